@@ -1,6 +1,6 @@
 """Benchmark: NPG update throughput (timesteps/s) on the Humanoid 1M-step batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,16 +16,26 @@ sampler's f64): batch assembly, GAE, whitening, forward +
 VPG, 10 Fisher-vector products + CG, step, post-step surrogate / KL, host
 readback of the statistics.  On one GPU an update of at most
 engine.GRAPH_AUTO_ROWS rows is replayed as one captured hipGraph (launch gaps
-dominate there; at 1M rows eager launches are faster), and the eager time is
-reported beside it (--graph on / off forces either).
+dominate there; at 1M rows eager launches are faster), and --full reports the
+eager time beside it (--graph on / off forces either).
 
 --config c2 / c3 / c5 runs the other BASELINE.json GPU shapes (Swimmer NPG,
 HalfCheetah TRPO with its line search, door DAPG with demonstrations) with their
 own metric names: per-config evidence, not the headline.
 
-Rank 0 prints one JSON line.  `roofline` is measured live with HIP events on the
-stream the kernels run on, `cpu_baseline` times the oracle (the CPU restatement
-of the reference update, oracle/npg_cpu.py) on a bounded sample on this host.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps
+and prints the headline (value, ms_per_step) with the run's configuration.
+--dump-outputs DIR also writes what the last timed step computed (DIR/<name>.npy,
+dump_outputs below); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+--full adds every companion measurement, each in runs of its own after the timed
+region: `roofline` is measured live with HIP events on the stream the kernels run
+on (with the eager time of a graphed update, eager_ms_per_step),
+`f32_ms_per_step` times the exact-f32 kernels, `e2e_from_host` / `e2e_stream`
+time the update from host paths, and `cpu_baseline` times the oracle (the CPU
+restatement of the reference update, oracle/npg_cpu.py) on this host.  The
+--no-* and --cpu-* options select among these and mean nothing without --full.
 """
 import argparse
 import json
@@ -540,126 +550,39 @@ def kernel_names(eng, cfg):
     return acc + (fl["rows_fvp"] + fl["weight_grads"], "k_gather", "k_gather", 0)
 
 
-def main():
-    # stdout carries the one JSON line and nothing else: libraries that print to
-    # fd 1 (RCCL's version banner at communicator init) are sent to stderr
-    json_out = os.fdopen(os.dup(1), "w")
-    sys.stdout.flush()
-    os.dup2(2, 1)
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
-    ap.add_argument("--paths", type=int, default=None, help="paths per update (default: the config's)")
-    ap.add_argument("--cpu-rows", type=int, default=None,
-                    help="timesteps of a bounded CPU-baseline sample (default: the config's full batch; about "
-                         "40 s per update at Humanoid 1M on 16 cores)")
-    ap.add_argument("--cpu-full", action="store_true", help="(the default) CPU baseline on the full batch")
-    ap.add_argument("--cpu-reps", type=int, default=None,
-                    help="timed CPU-baseline updates (default: 3 at c4, 10 for the smaller configs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end-from-host-paths measurement")
-    ap.add_argument("--no-f32", action="store_true", help="skip the exact-f32 companion timing")
-    ap.add_argument("--stage-dtype", choices=("f32", "f64"), default="f32",
-                    help="observations / actions of the device-resident batch: f32 as train_step stages them "
-                         "(BatchREINFORCE.staging_dtype), or the sampler's f64")
-    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
-                    help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 "
-                         "path with several ranks on one GPU)")
-    ap.add_argument("--comm", default="rccl", choices=["rccl", "torch"],
-                    help="N > 1 over nccl: RCCL driven directly on the update's stream (comm.RcclComm: the "
-                         "sharded update is one captured hipGraph, collectives inside) or torch.distributed's "
-                         "own collectives (eager)")
-    ap.add_argument("--sharded-path", action="store_true",
-                    help="one GPU: run the sharded code path on a one-rank RCCL communicator (all-gathered "
-                         "moments, an all-reduce between every FVP and its CG step, RCCL calls inside the "
-                         "captured graph) -- the per-rank schedule of an N-GPU run, on this GPU's shard")
-    ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
-                    help="replay each update as one captured hipGraph (one GPU): auto = the engine's "
-                         "default, graphs for batches up to engine.GRAPH_AUTO_ROWS rows")
-    ap.add_argument("--precision", default=None, choices=["auto", "split", "f32"],
-                    help="first-layer MFMA form (UpdateEngine precision; default: split where supported)")
-    args = ap.parse_args()
-    cfg = dict(CONFIGS[args.config])
-    if args.paths:
-        cfg["paths"] = args.paths
-    n, m, hidden, H = cfg["n"], cfg["m"], cfg["hidden"], cfg["horizon"]
+DUMP_STATS = ("alpha", "gx", "delta", "surr_before", "surr_after", "kl_dist", "cg_iters")
+DUMP_MAX_ROWS = 4 << 20   # elements kept of one array: 32 MB of f64, under --dump-outputs' 64 MB in all
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    ndev = max(torch.cuda.device_count(), 1)
-    dev_idx = local % ndev if args.backend == "gloo" else local
-    torch.cuda.set_device(dev_idx)
-    device = torch.device("cuda", dev_idx)
-    comm = None
-    if world > 1:
-        import torch.distributed as dist
-        if args.backend == "nccl":
-            dist.init_process_group("nccl", device_id=device)
-        else:
-            dist.init_process_group("gloo")
-        from mjrl_amd.comm import DistComm, RcclComm
-        comm = RcclComm(device) if args.backend == "nccl" and args.comm == "rccl" else DistComm()
-    elif args.sharded_path:
-        from mjrl_amd.comm import RcclComm
-        comm = RcclComm.local(device)
-    from mjrl_amd.comm import partition_paths
-    from mjrl_amd.engine import UpdateEngine
 
-    base = baseline_coeffs(cfg)
-    p0, p1 = partition_paths(np.full(cfg["paths"], H), world)[rank]
-    batch = stage_shard(p0, p1, device, base, cfg, demo_share(cfg, rank, world),
-                        np.float32 if args.stage_dtype == "f32" else np.float64)
-    T_total = cfg["paths"] * H
+def dump_outputs(path, eng, res, T):
+    """What one update hands its caller, as path/<name>.npy: the new parameters,
+    the policy gradient and the natural-gradient direction behind them (f32, the
+    policy's own parameter order), this rank's GAE advantages before whitening
+    (f64; beyond DUMP_MAX_ROWS rows a fixed seeded sample of them), and
+    the update's host scalars in DUMP_STATS order followed by the four path-return
+    statistics (f64)."""
+    os.makedirs(path, exist_ok=True)
+    vec = eng.vec
+    adv = eng.ws["adv64"][:T]
+    if T > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(T, DUMP_MAX_ROWS, replace=False))
+        adv = adv[torch.from_numpy(rows).to(adv.device)]
+    arrays = dict(theta_new=vec["theta_new"], vpg_grad=vec["g"], npg_grad=vec["x"], advantages=adv)
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays["stats"] = np.array([float(res[k]) for k in DUMP_STATS] + [float(x) for x in res["base_stats"]], np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    log("outputs of the last timed step written to %s: %s" % (path, ", ".join(sorted(arrays))))
 
-    eng = UpdateEngine(n, m, hidden, device=device, comm=comm, precision=args.precision)
-    th0 = torch.from_numpy(initial_theta(cfg)).to(device)
-    th = th0.clone()
-    upd = update_args(cfg, T_total)
-    eng.graphs = {"auto": "auto", "on": True, "off": False}[args.graph]
-    # per-FVP (start, accumulate done, gather done) events on eager steps; a captured
-    # graph is kept free of them (30 event nodes per update measured +3 % on the
-    # replay) and the kernel timings come from eager steps after the timed region
-    eng.kernel_timing = None if eng.graphs else []
 
-    def step(graph=None, e=eng):
-        nonlocal th
-        e.update(batch, th, graph=graph, **upd)
-        th = e.vec["theta_new"].clone()
-
-    for _ in range(args.warmup):
-        step()
-    if eng.kernel_timing is not None:
-        eng.kernel_timing.clear()
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    elapsed = time.perf_counter() - t0
-    log("timed region: %d steps, %.3f ms per step" % (args.steps, elapsed / args.steps * 1e3))
-    per_rank = [dict(rank=rank, rows=batch.T, ms_per_step=round(elapsed / args.steps * 1e3, 3))]
-    if world > 1:
-        # every rank's own rows and time (so the line shows the shards and how far
-        # apart the ranks finished), then the max over ranks as the job's time
-        t = torch.tensor([float(rank), float(batch.T), elapsed], dtype=torch.float64,
-                         device=device if args.backend == "nccl" else "cpu")
-        allt = [torch.zeros_like(t) for _ in range(world)]
-        torch.distributed.all_gather(allt, t)
-        per_rank = [dict(rank=int(a[0]), rows=int(a[1]), ms_per_step=round(float(a[2]) / args.steps * 1e3, 3))
-                    for a in (x.cpu().numpy() for x in allt)]
-        elapsed = max(float(x[2].item()) for x in allt)
-
+def roofline(args, cfg, eng, step, rows_rank, elapsed, world, graphed):
+    """(roofline, eager_ms_per_step) of --full.  `step` runs one more update,
+    `elapsed` is the timed region's seconds over args.steps steps."""
+    n, m, hidden = cfg["n"], cfg["m"], cfg["hidden"]
+    T_total = cfg["paths"] * cfg["horizon"]
     # dominant-kernel roofline from live HIP events on the launch stream, recorded
     # around every FVP of eager steps: the timed region's when it ran eager, else
     # the same update run eagerly after it (which also gives eager_ms_per_step)
-    graphed = bool(eng.graphs) and eng._gstate.get("graph") is not None
     samples = [] if eng.kernel_timing is None else \
         [(a.elapsed_time(b), b.elapsed_time(c)) for a, b, c in eng.kernel_timing]
     eager_ms = None
@@ -681,7 +604,6 @@ def main():
     t_acc = np.mean([a for a, _ in samples]) / 1e3
     t_gat = np.mean([b for _, b in samples]) / 1e3
     acc_name, acc_key, acc_fl, gat_name, gat_key, gat_fl = kernel_names(eng, cfg)
-    rows_rank = batch.T
     np_ = eng.shape.np
     h0, h1 = hidden
     # algorithmic HBM bytes per row of one FVP launch: the observation row (f32, or the
@@ -735,10 +657,145 @@ def main():
                           note="algorithmic FLOPs of a whole update / wall time per update, vs n_gpus x the "
                                "matrix peak of the form the kernels use (frac); frac_of_exact_f32_peak prices "
                                "the same FLOPs against the exact-f32 MFMA peak, for comparison only")
+    return roof, eager_ms
+
+
+def main():
+    # stdout carries the one JSON line and nothing else: libraries that print to
+    # fd 1 (RCCL's version banner at communicator init) are sent to stderr
+    json_out = os.fdopen(os.dup(1), "w")
+    sys.stdout.flush()
+    os.dup2(2, 1)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy "
+                         "(dump_outputs; rank 0's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline of the dominant kernel, the eager and "
+                         "exact-f32 companion timings, the end-to-end updates from host paths and the CPU baseline")
+    ap.add_argument("--paths", type=int, default=None, help="paths per update (default: the config's)")
+    ap.add_argument("--cpu-rows", type=int, default=None,
+                    help="timesteps of a bounded CPU-baseline sample (default: the config's full batch; about "
+                         "40 s per update at Humanoid 1M on 16 cores)")
+    ap.add_argument("--cpu-full", action="store_true", help="(the default) CPU baseline on the full batch")
+    ap.add_argument("--cpu-reps", type=int, default=None,
+                    help="timed CPU-baseline updates (default: 3 at c4, 10 for the smaller configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end-from-host-paths measurement")
+    ap.add_argument("--no-f32", action="store_true", help="skip the exact-f32 companion timing")
+    ap.add_argument("--stage-dtype", choices=("f32", "f64"), default="f32",
+                    help="observations / actions of the device-resident batch: f32 as train_step stages them "
+                         "(BatchREINFORCE.staging_dtype), or the sampler's f64")
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
+                    help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 "
+                         "path with several ranks on one GPU)")
+    ap.add_argument("--comm", default="rccl", choices=["rccl", "torch"],
+                    help="N > 1 over nccl: RCCL driven directly on the update's stream (comm.RcclComm: the "
+                         "sharded update is one captured hipGraph, collectives inside) or torch.distributed's "
+                         "own collectives (eager)")
+    ap.add_argument("--sharded-path", action="store_true",
+                    help="one GPU: run the sharded code path on a one-rank RCCL communicator (all-gathered "
+                         "moments, an all-reduce between every FVP and its CG step, RCCL calls inside the "
+                         "captured graph) -- the per-rank schedule of an N-GPU run, on this GPU's shard")
+    ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
+                    help="replay each update as one captured hipGraph (one GPU): auto = the engine's "
+                         "default, graphs for batches up to engine.GRAPH_AUTO_ROWS rows")
+    ap.add_argument("--precision", default=None, choices=["auto", "split", "f32"],
+                    help="first-layer MFMA form (UpdateEngine precision; default: split where supported)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    cfg = dict(CONFIGS[args.config])
+    if args.paths:
+        cfg["paths"] = args.paths
+    n, m, hidden, H = cfg["n"], cfg["m"], cfg["hidden"], cfg["horizon"]
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    ndev = max(torch.cuda.device_count(), 1)
+    dev_idx = local % ndev if args.backend == "gloo" else local
+    torch.cuda.set_device(dev_idx)
+    device = torch.device("cuda", dev_idx)
+    comm = None
+    if world > 1:
+        import torch.distributed as dist
+        if args.backend == "nccl":
+            dist.init_process_group("nccl", device_id=device)
+        else:
+            dist.init_process_group("gloo")
+        from mjrl_amd.comm import DistComm, RcclComm
+        comm = RcclComm(device) if args.backend == "nccl" and args.comm == "rccl" else DistComm()
+    elif args.sharded_path:
+        from mjrl_amd.comm import RcclComm
+        comm = RcclComm.local(device)
+    from mjrl_amd.comm import partition_paths
+    from mjrl_amd.engine import UpdateEngine
+
+    base = baseline_coeffs(cfg)
+    p0, p1 = partition_paths(np.full(cfg["paths"], H), world)[rank]
+    batch = stage_shard(p0, p1, device, base, cfg, demo_share(cfg, rank, world),
+                        np.float32 if args.stage_dtype == "f32" else np.float64)
+    T_total = cfg["paths"] * H
+
+    eng = UpdateEngine(n, m, hidden, device=device, comm=comm, precision=args.precision)
+    th0 = torch.from_numpy(initial_theta(cfg)).to(device)
+    th = th0.clone()
+    upd = update_args(cfg, T_total)
+    eng.graphs = {"auto": "auto", "on": True, "off": False}[args.graph]
+    # per-FVP (start, accumulate done, gather done) events on eager steps; a captured
+    # graph is kept free of them (30 event nodes per update measured +3 % on the
+    # replay) and the kernel timings come from eager steps after the timed region
+    eng.kernel_timing = None if eng.graphs else []
+
+    res = None
+
+    def step(graph=None, e=eng):
+        nonlocal th, res
+        res = e.update(batch, th, graph=graph, **upd)
+        th = e.vec["theta_new"].clone()
+
+    for _ in range(args.warmup):
+        step()
+    if eng.kernel_timing is not None:
+        eng.kernel_timing.clear()
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    torch.cuda.synchronize()
+    if world > 1:
+        torch.distributed.barrier()
+    elapsed = time.perf_counter() - t0
+    log("timed region: %d steps, %.3f ms per step" % (args.steps, elapsed / args.steps * 1e3))
+    per_rank = [dict(rank=rank, rows=batch.T, ms_per_step=round(elapsed / args.steps * 1e3, 3))]
+    if world > 1:
+        # every rank's own rows and time (so the line shows the shards and how far
+        # apart the ranks finished), then the max over ranks as the job's time
+        t = torch.tensor([float(rank), float(batch.T), elapsed], dtype=torch.float64,
+                         device=device if args.backend == "nccl" else "cpu")
+        allt = [torch.zeros_like(t) for _ in range(world)]
+        torch.distributed.all_gather(allt, t)
+        per_rank = [dict(rank=int(a[0]), rows=int(a[1]), ms_per_step=round(float(a[2]) / args.steps * 1e3, 3))
+                    for a in (x.cpu().numpy() for x in allt)]
+        elapsed = max(float(x[2].item()) for x in allt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, res, batch.T)
+
+    graphed = bool(eng.graphs) and eng._gstate.get("graph") is not None
+    roof = eager_ms = None
+    if args.full:
+        roof, eager_ms = roofline(args, cfg, eng, step, batch.T, elapsed, world, graphed)
 
     # the same update on the exact-f32 MFMA kernels (precision='f32'), for reference
     f32_ms = None
-    if world == 1 and eng.precision == "split" and not args.no_f32:
+    if args.full and world == 1 and eng.precision == "split" and not args.no_f32:
         log("exact-f32 companion timing")
         e32 = UpdateEngine(n, m, hidden, device=device, precision="f32")
         e32.graphs = eng.graphs
@@ -776,14 +833,14 @@ def main():
                    comm_backend=(torch.distributed.get_backend() if world > 1 else None),
                    hipgraph=bool(graphed), eager_ms_per_step=None if eager_ms is None else round(eager_ms, 3),
                    f32_ms_per_step=None if f32_ms is None else round(f32_ms, 3),
-                   roofline=roof)
-        if world == 1 and not args.no_e2e and cfg["algo"] != "dapg":
+                   roofline=roof, full=args.full)
+        if args.full and world == 1 and not args.no_e2e and cfg["algo"] != "dapg":
             th = th0.clone()
             log("end-to-end from host paths")
             out["e2e_from_host"] = e2e_from_host((p0, p1), eng, th, base, upd, device, cfg)
             log("end-to-end with the sampler feeding the staging")
             out["e2e_stream"] = e2e_stream((p0, p1), eng, th0, base, upd, device, cfg)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rows = T_total if (args.cpu_full or not args.cpu_rows) else min(args.cpu_rows, T_total)
             reps = args.cpu_reps or (3 if args.config == "c4" else 10)
             out["cpu_baseline"] = cpu_baseline(rows, base, reps=reps, cfg=cfg)
