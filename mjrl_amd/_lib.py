@@ -4,6 +4,12 @@ The library is mjrl_amd/lib/libmjrl_amd.so, built in-tree by
 `python -m mjrl_amd.build` (or __graft_entry__.build()).  There is no CPU
 fallback: if the library or a GPU is missing, `lib()` raises.
 
+Two handles per library: the raw one (`load()` / `lib()` / `stage_lib()`: plain
+argtypes, int returns; tests and tools/ time and probe single entry points
+through it) and the checked one the package itself calls through (`calls()` /
+`stage_calls()`: tensors and structures passed as they are, MjrlError on a bad
+status).
+
 torch is imported first on purpose: torch-ROCm ships the HIP runtime
 (libamdhip64.so.7) and our library resolves against that already-loaded copy, so
 torch's hipStream_t handles are valid arguments.
@@ -193,6 +199,71 @@ def check(rc, what):
         msg = {MJRL_EINVAL: "invalid argument", MJRL_ESHAPE: "unsupported policy shape"}.get(
             rc, "HIP error %d" % rc)
         raise MjrlError("%s failed: %s" % (what, msg))
+
+
+# entry points whose int result is an answer, not a status: no errcheck
+QUERIES = ("mjrl_fused_path", "mjrl_split_supported", "mjrl_build_flags", "mjrl_host_stage_avx512")
+_CALLS = {}
+
+
+class _DevPtr:
+    """A `P` slot of the checked handles: None, a torch.Tensor (its data_ptr()),
+    a c_void_p or an int.  No validation the raw path does not have."""
+
+    @staticmethod
+    def from_param(v, _T=torch.Tensor, _vp=C.c_void_p):
+        if type(v) is _T:   # first: the hot path (an eager update is launch-bound)
+            return _vp(v.data_ptr())
+        if v is None or type(v) is _vp:
+            return v
+        if isinstance(v, _T):
+            return _vp(v.data_ptr())
+        return _vp.from_param(v)   # int (and whatever else c_void_p itself takes)
+
+
+class _HostPtr:
+    """A `P` slot of the host library: as _DevPtr, and a numpy array (its
+    .ctypes.data) or a ctypes array."""
+
+    @staticmethod
+    def from_param(v, _vp=C.c_void_p):
+        c = getattr(v, "ctypes", None)   # numpy
+        return _vp(c.data) if c is not None else _DevPtr.from_param(v)
+
+
+def _errcheck(rc, fn, args):
+    if rc:
+        check(rc, fn.__name__)
+    return rc
+
+
+def _checked(path, names, ptr):
+    """A second CDLL object over `path`: its function objects are its own, so
+    they carry converting argtypes (`ptr` in the P slots; the POINTER(struct)
+    slots take the structure itself or a byref, as ctypes pointers do) and an
+    errcheck that raises MjrlError under the entry point's own name."""
+    h = _CALLS.get(path)
+    if h is None:
+        h = _CALLS[path] = C.CDLL(path)
+        for name in names:
+            fn = getattr(h, name)
+            fn.argtypes = [ptr if a is P else a for a in SIGNATURES[name]]
+            fn.restype = C.c_int
+            if name not in QUERIES:
+                fn.errcheck = _errcheck
+    return h
+
+
+def calls(loader=lib):
+    """The checked handle of the HIP library: K.mjrl_x(tensor, n, None, shape,
+    stream) converts its arguments from SIGNATURES and raises on a bad status.
+    Refuses without a GPU as lib() does (loader=load: no refusal)."""
+    return _checked(loader()._name, SIGNATURES, _DevPtr)
+
+
+def stage_calls():
+    """The checked handle of the host-only staging library."""
+    return _checked(stage_lib()._name, STAGE_FUNCS, _HostPtr)
 
 
 def make_shape(n, m, h0, h1, loader=load):

@@ -11,6 +11,7 @@ Reference this replaces: mjrl/algos/npg_cg.py:84-165 (NPG.train_from_paths),
 mjrl/algos/trpo.py:54-145, mjrl/algos/dapg.py:54-141,
 mjrl/algos/batch_reinforce.py:106-164, mjrl/utils/process_samples.py:3-44.
 """
+import collections
 import ctypes as C
 import functools
 import math
@@ -95,8 +96,8 @@ def host_stage(arrs, view, offs, a0, a1, lo=None, hi=None, extras=None):
     converted to it first, so the extras always come from the values as given."""
     fns = None
     if view.dtype == np.float32 and view.ndim == 2:
-        L = _lib.stage_lib()
-        fns = {np.dtype(np.float64): L.mjrl_host_stage_f64, np.dtype(np.float32): L.mjrl_host_stage_f32}
+        S = _lib.stage_calls()
+        fns = {np.dtype(np.float64): S.mjrl_host_stage_f64, np.dtype(np.float32): S.mjrl_host_stage_f32}
         # the common case, every array of the chunk C-contiguous f64 of the view's
         # width: one native call for the whole chunk
         srcs = [np.asarray(arrs[i]) for i in range(a0, a1)]
@@ -110,17 +111,15 @@ def host_stage(arrs, view, offs, a0, a1, lo=None, hi=None, extras=None):
             ptrs = (C.c_void_p * k)(*[a.ctypes.data for a in srcs])
             rows = (C.c_int64 * k)(*[a.shape[0] for a in srcs])
             dst = view[offs[a0]:offs[a1]]
-            rng = (None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data)
             if dst.shape[0] and extras is None:
-                _lib.check(L.mjrl_host_stage_paths_f64(ptrs, rows, k, n, dst.ctypes.data, *rng), "mjrl_host_stage")
+                S.mjrl_host_stage_paths_f64(ptrs, rows, k, n, dst, lo, hi)
             elif dst.shape[0]:
                 npred = max(0, min(a1, int(extras["npred"])) - a0)
                 c = extras.get("coeffs")
                 withp = c is not None and npred > 0
-                _lib.check(L.mjrl_host_stage_paths_f64x(
-                    ptrs, rows, k, n, dst.ctypes.data, *rng, c.ctypes.data if withp else None,
-                    extras["pred"][offs[a0]:].ctypes.data if withp else None, npred if withp else 0,
-                    extras["flag"].ctypes.data), "mjrl_host_stage")
+                S.mjrl_host_stage_paths_f64x(ptrs, rows, k, n, dst, lo, hi, c if withp else None,
+                                             extras["pred"][offs[a0]:] if withp else None, npred if withp else 0,
+                                             extras["flag"])
             return
         if extras is not None:
             raise ValueError("host_stage extras: observation arrays of a path do not match the staged width %d" % n)
@@ -138,7 +137,7 @@ def host_stage(arrs, view, offs, a0, a1, lo=None, hi=None, extras=None):
                 k = len(srcs)
                 ptrs = (C.c_void_p * k)(*[a.ctypes.data for a in srcs])
                 nb = (C.c_int64 * k)(*[a.nbytes for a in srcs])
-                _lib.check(_lib.stage_lib().mjrl_host_gather(ptrs, nb, k, dst.ctypes.data), "mjrl_host_gather")
+                _lib.stage_calls().mjrl_host_gather(ptrs, nb, k, dst)
                 return
             np.concatenate(srcs, out=dst)
             if lo is not None and view.ndim == 2 and offs[a1] > offs[a0]:
@@ -153,9 +152,7 @@ def host_stage(arrs, view, offs, a0, a1, lo=None, hi=None, extras=None):
         src = np.asarray(arrs[i])
         fn = fns.get(src.dtype) if fns is not None else None
         if fn is not None and src.ndim == 2 and src.shape == dst.shape and src.flags.c_contiguous:
-            rc = fn(src.ctypes.data, dst.shape[0], dst.shape[1], dst.ctypes.data,
-                    None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data)
-            _lib.check(rc, "mjrl_host_stage")
+            fn(src, dst.shape[0], dst.shape[1], dst, lo, hi)
             continue
         np.copyto(dst, src.reshape(dst.shape), casting="unsafe")
         if lo is not None:
@@ -174,8 +171,7 @@ def host_stage_lo(arrs, view, offs, a0, a1):
     k = len(srcs)
     ptrs = (C.c_void_p * k)(*[a.ctypes.data for a in srcs])
     rows = (C.c_int64 * k)(*[a.shape[0] for a in srcs])
-    _lib.check(_lib.stage_lib().mjrl_host_stage_lo_paths_f64(ptrs, rows, k, view.shape[1], dst.ctypes.data),
-               "mjrl_host_stage_lo_paths_f64")
+    _lib.stage_calls().mjrl_host_stage_lo_paths_f64(ptrs, rows, k, view.shape[1], dst)
 
 
 class _PinnedStaging:
@@ -450,6 +446,26 @@ def _on_device(fn):
     return wrapped
 
 
+# the arguments of one update, as its stages read them (UpdateEngine._launch).  The
+# fields between batch and T_global are, in this order, the argument part of the
+# graph key (_graph_key); sub: the Fisher subsample's draws (_hvp_draws) or None
+_Update = collections.namedtuple("_Update", (
+    "batch", "algo", "gamma", "gae_lambda", "n_step_size", "const_lr", "kl_dist", "cg_iters", "damping",
+    "residual_tol", "learn_rate", "skip_gae", "demo_coef", "T_global", "sub"))
+
+
+def _normalize(K, x, T, part, m1, m2, out, st, allreduce=None):
+    """out = (x - mean) / (std + 1e-8) over the T f64 values of x
+    (process_samples.py:14-19, 30-35): two-pass fp64 moments into the records m1 /
+    m2 (pass 2 about pass 1's mean; `part`: the passes' scratch), each pass's sums
+    all-reduced when `allreduce` is given, then mjrl_whiten; all on stream st."""
+    for center, m in ((None, m1), (m1, m2)):
+        K.mjrl_moments(x, T, center, part, m, st)
+        if allreduce is not None:
+            allreduce(m[:3])
+    K.mjrl_whiten(x, T, m1, m2, 1e-8, None, out, st)
+
+
 class DeviceBatch:
     """One shard of trajectories in HBM — the hot path's input.
 
@@ -561,10 +577,9 @@ class DeviceBatch:
             base.zero_()
             if coeffs is not None and T > 0:
                 c = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64)).to(device)
-                fn = _lib.lib().mjrl_linear_baseline_f32 if obs.dtype == torch.float32 else \
-                    _lib.lib().mjrl_linear_baseline
-                _lib.check(fn(_lib.ptr(obs), T, n, _lib.ptr(off), len(paths), _lib.ptr(c), _lib.ptr(base),
-                              _lib.stream_ptr()), "mjrl_linear_baseline")
+                K = _lib.calls()
+                fn = K.mjrl_linear_baseline_f32 if obs.dtype == torch.float32 else K.mjrl_linear_baseline
+                fn(obs, T, n, off, len(paths), c, base, _lib.stream_ptr())
             adv = None
         elif hasattr(baseline, "predict_device"):
             # MLPBaseline: one device forward over every staged row
@@ -670,7 +685,8 @@ class UpdateEngine:
         split-f16 MFMA (hi*hi + hi*lo + lo*hi, f32 accumulate), 'f32'
         on exact-f32 MFMA; default (None / 'auto', or $MJRL_AMD_PRECISION): split
         wherever the kernels support it (mjrl_split_supported), f32 elsewhere."""
-        self.lib = _lib.lib()
+        self.lib = _lib.lib()   # the raw handle (tools/ time single entry points through it)
+        self.K = _lib.calls()   # the checked handle every launch below goes through
         real = (0, 0) if hidden is None else (int(hidden[0]), int(hidden[1]))
         kh = kernel_hidden(int(n), int(m), hidden)
         self.shape = _lib.make_shape(int(n), int(m), *kh)
@@ -717,11 +733,11 @@ class UpdateEngine:
         self.graphs = "auto"
         self._gstate = {}
         self.gae_mode = os.environ.get("MJRL_AMD_GAE", "serial")   # "serial" (exact) or "scan"
-        self.fused = bool(self.lib.mjrl_fused_path(C.byref(self.shape)))
+        self.fused = bool(self.K.mjrl_fused_path(self.shape))
         prec = precision or os.environ.get("MJRL_AMD_PRECISION", "auto")
         if prec not in ("auto", "split", "f32"):
             raise ValueError("precision must be 'auto', 'split' or 'f32', got %r" % (prec,))
-        can_split = bool(self.lib.mjrl_split_supported(C.byref(self.shape)))
+        can_split = bool(self.K.mjrl_split_supported(self.shape))
         if prec == "split" and not can_split:
             raise ValueError("split precision is not available for this policy shape")
         self.split = can_split and prec != "f32"
@@ -814,24 +830,25 @@ class UpdateEngine:
         w["mu0"] = torch.empty((T_all, s.m), **f32)
         w["ll0"] = torch.empty(T_all, **f32)
         w["gp"] = torch.empty((T_all, s.mp), **f32)
-        wf, rd, sl = C.c_int64(), C.c_int64(), C.c_int32()
-        _lib.check(self.lib.mjrl_scratch_size(C.byref(s), T_all, C.byref(wf), C.byref(rd), C.byref(sl)),
-                   "mjrl_scratch_size")
-        w["wpart"] = torch.empty(max(wf.value, 1), **f32)
-        w["rpart"] = torch.zeros(max(rd.value, 1), **f64)
-        self.scratch_slices = sl.value
+        wf, rd, self.scratch_slices = self._scratch_size(T_all)
+        w["wpart"] = torch.empty(max(wf, 1), **f32)
+        w["rpart"] = torch.zeros(max(rd, 1), **f64)
         self.cap_T, self.cap_P = T_all, P
+
+    def _scratch_size(self, T):
+        """(wpart floats, rpart doubles, slices) of a pass over T rows."""
+        wf, rd, sl = C.c_int64(), C.c_int64(), C.c_int32()
+        self.K.mjrl_scratch_size(self.shape, T, wf, rd, sl)
+        return wf.value, rd.value, sl.value
 
     def _scratch(self, T, ws=None):
         """Scratch of a pass over T rows, in ws (default: the main workspace; the
         caller guarantees ws holds mjrl_scratch_size(T)'s wpart / rpart)."""
         ws = self.ws if ws is None else ws
-        wf, rd, sl = C.c_int64(), C.c_int64(), C.c_int32()
-        self.lib.mjrl_scratch_size(C.byref(self.shape), T, C.byref(wf), C.byref(rd), C.byref(sl))
         sc = _lib.Scratch()
         sc.wpart = ws["wpart"].data_ptr()
         sc.rpart = ws["rpart"].data_ptr()
-        sc.slices = sl.value
+        sc.slices = self._scratch_size(T)[2]
         return sc
 
     def _rows(self, T, adv_vpg):
@@ -850,17 +867,6 @@ class UpdateEngine:
         r.adv_vpg = adv_vpg.data_ptr()
         return r
 
-    def _stat(self, slot, n=3):
-        return self.stats[slot:slot + n]
-
-    def _moments(self, x, N, out_slot, center_slot=None, f32=False, reduce=True):
-        fn = self.lib.mjrl_moments_f32 if f32 else self.lib.mjrl_moments
-        center = None if center_slot is None else C.c_void_p(self.stats[center_slot:].data_ptr())
-        _lib.check(fn(_lib.ptr(x), N, center, _lib.ptr(self.mom_part),
-                      C.c_void_p(self.stats[out_slot:].data_ptr()), self.st), "mjrl_moments")
-        if reduce:
-            self.comm.allreduce_sum(self._stat(out_slot))
-
     def _reduce_stats(self, a, b):
         """SUM all-reduce of the contiguous stats slots [a, b) (sharded only)."""
         if self.sharded:
@@ -873,9 +879,7 @@ class UpdateEngine:
         W = self.comm.world_size
         g = self.gbuf[:W * rec]
         self.comm.allgather(self.stats[base:base + rec], g)
-        _lib.check(self.lib.mjrl_moments_combine(_lib.ptr(g), W, rec, ngroups,
-                                                 C.c_void_p(self.stats[base:].data_ptr()), st),
-                   "mjrl_moments_combine")
+        self.K.mjrl_moments_combine(g, W, rec, ngroups, self.stats[base:], st)
 
     def _fused_pack(self, batch, T_all, T_vpg):
         """Whether this update's forward pass assembles the split rows itself
@@ -891,38 +895,31 @@ class UpdateEngine:
     def _colscale(self, obs, T, st, obs_range=None):
         """The split rows' power-of-two column scales of this batch (w['xc']):
         from the staged per-column ranges (no pass over obs), or a device pass."""
-        w = self.ws
+        K, xc = self.K, self.ws["xc"]
         ins, isc, _, _ = self.transforms
-        sp = C.byref(self.shape)
         if obs_range is not None:
-            _lib.check(self.lib.mjrl_obs_colscale_range(_lib.ptr(obs_range[0]), _lib.ptr(obs_range[1]), sp,
-                                                        _lib.ptr(ins), _lib.ptr(isc), _lib.ptr(w["xc"]), st),
-                       "mjrl_obs_colscale_range")
+            K.mjrl_obs_colscale_range(obs_range[0], obs_range[1], self.shape, ins, isc, xc, st)
         else:
-            cs = self.lib.mjrl_obs_colscale_f32 if obs.dtype == torch.float32 else self.lib.mjrl_obs_colscale
-            _lib.check(cs(_lib.ptr(obs), T, sp, _lib.ptr(ins), _lib.ptr(isc), _lib.ptr(w["xc"]), st),
-                       "mjrl_obs_colscale")
+            cs = K.mjrl_obs_colscale_f32 if obs.dtype == torch.float32 else K.mjrl_obs_colscale
+            cs(obs, T, self.shape, ins, isc, xc, st)
 
     def _pack(self, obs, act, T, st, obs_range=None):
         """a5 batch assembly: f64 obs / act -> the row format the policy passes read.
         obs_range: the staged batch's per-column (min, max) (DeviceBatch.obs_range),
         from which the split rows' column scales follow without a pass over obs."""
-        w = self.ws
+        K, w = self.K, self.ws
         ins, isc, _, _ = self.transforms
-        sp = C.byref(self.shape)
         f32 = obs.dtype == torch.float32
         if f32 != (act.dtype == torch.float32):
             raise ValueError("observations and actions must be staged in the same dtype")
         if self.split:
             # column scales of this batch, then the split rows
             self._colscale(obs, T, st, obs_range)
-            fn = self.lib.mjrl_pack_batch_split_f32 if f32 else self.lib.mjrl_pack_batch_split
-            _lib.check(fn(_lib.ptr(obs), _lib.ptr(act), T, sp, _lib.ptr(ins), _lib.ptr(isc), _lib.ptr(w["xc"]),
-                          _lib.ptr(w["xs"]), _lib.ptr(w["xu"]), _lib.ptr(w["act32"]), st), "mjrl_pack_batch_split")
+            fn = K.mjrl_pack_batch_split_f32 if f32 else K.mjrl_pack_batch_split
+            fn(obs, act, T, self.shape, ins, isc, w["xc"], w["xs"], w["xu"], w["act32"], st)
         else:
-            fn = self.lib.mjrl_pack_batch_f32 if f32 else self.lib.mjrl_pack_batch
-            _lib.check(fn(_lib.ptr(obs), _lib.ptr(act), T, sp, _lib.ptr(ins), _lib.ptr(isc), _lib.ptr(w["xhat"]),
-                          _lib.ptr(w["act32"]), st), "mjrl_pack_batch")
+            fn = K.mjrl_pack_batch_f32 if f32 else K.mjrl_pack_batch
+            fn(obs, act, T, self.shape, ins, isc, w["xhat"], w["act32"], st)
 
     # ------------------------------------------------------------------
     def _side_stream(self):
@@ -936,19 +933,15 @@ class UpdateEngine:
         Leaves f64 returns / advantages in ws['ret'] / ws['adv64'].  `stream`: run on
         that HIP stream (update() overlaps the scan with the batch assembly)."""
         st = stream if stream is not None else _lib.stream_ptr()
-        if stream is None:
-            self.st = st
         self._ensure(batch.T + batch.T_demo, batch.P)
         w = self.ws
         use_gae = not (gae_lambda is None or gae_lambda < 0.0 or gae_lambda > 1.0)
         base = self._baseline_of(batch)
         # "serial": discount_sum's operation order bit for bit (the default); "scan":
         # the wave-parallel scan (regrouped products, ~1e-14 relative)
-        fn = self.lib.mjrl_gae_scan if self.gae_mode == "scan" else self.lib.mjrl_gae
-        _lib.check(fn(
-            _lib.ptr(batch.rewards), _lib.ptr(base), _lib.ptr(batch.path_off), _lib.ptr(batch.terminated),
-            batch.P, float(gamma), float(gae_lambda) if use_gae else 0.0, int(use_gae),
-            _lib.ptr(w["ret"]), _lib.ptr(w["adv64"]), _lib.ptr(w["path_ret"]), st), "mjrl_gae")
+        fn = self.K.mjrl_gae_scan if self.gae_mode == "scan" else self.K.mjrl_gae
+        fn(batch.rewards, base, batch.path_off, batch.terminated, batch.P, float(gamma),
+           float(gae_lambda) if use_gae else 0.0, int(use_gae), w["ret"], w["adv64"], w["path_ret"], st)
         return w["ret"][:batch.T], w["adv64"][:batch.T]
 
     @staticmethod
@@ -964,11 +957,8 @@ class UpdateEngine:
     def normalize_advantages(self, T):
         """The `normalize` option of compute_advantages (process_samples.py:14-19,30-35)."""
         w = self.ws
-        self._moments(w["adv64"], T, S_M1)
-        self._moments(w["adv64"], T, S_M2, center_slot=S_M1)
-        _lib.check(self.lib.mjrl_whiten(_lib.ptr(w["adv64"]), T, C.c_void_p(self.stats[S_M1:].data_ptr()),
-                                        C.c_void_p(self.stats[S_M2:].data_ptr()), 1e-8, None,
-                                        _lib.ptr(w["w64"]), self.st), "mjrl_whiten")
+        _normalize(self.K, w["adv64"], T, self.mom_part, self.stats[S_M1:], self.stats[S_M2:], w["w64"],
+                   _lib.stream_ptr(), self.comm.allreduce_sum)
         return w["w64"][:T]
 
     @_on_device
@@ -992,12 +982,9 @@ class UpdateEngine:
         subsampled Fisher; TRPO's line search continues on the host after the
         replayed graph, which ends at the first evaluation; see _maybe_capture).
         Returns host scalars plus the new device theta (self.vec['theta_new'])."""
-        L = self.lib
-        s = self.shape
-        self.st = st = _lib.stream_ptr()
+        st = _lib.stream_ptr()   # the host continuation's (_trpo_search); _launch reads its own
         theta = self._pad(theta, "theta")
-        T, T_demo, P = batch.T, batch.T_demo, batch.P
-        T_all = T + T_demo
+        T, T_all = batch.T, batch.T + batch.T_demo
         # global row count (all ranks): scales every mean; one host round trip per
         # staged batch, cached on it (outside any captured graph)
         if T_global is None and self.comm.world_size > 1:
@@ -1008,27 +995,23 @@ class UpdateEngine:
                 T_global = batch.T_global = float(tg.item())
         elif T_global is None:
             T_global = float(T)
-        sharded = self.sharded
         sub = None
         if hvp_sample_frac is not None and hvp_sample_frac < 0.99 and algo != "vpg":
             sub = self._hvp_draws(float(hvp_sample_frac), int(round(T_global)), T, int(cg_iters))
         # a subsampled Fisher's rows live in ws_sub (_subsample_rows), so the main
         # workspace keeps its size and the GAE outputs already in it
-        self._ensure(T_all, P)
-        w = self.ws
-        v = self.pvec
-        sp = C.byref(s)
-        ins, isc, osh, osc = self.transforms
+        self._ensure(T_all, batch.P)
+        u = _Update(batch, algo, gamma, gae_lambda, n_step_size, const_lr, kl_dist, cg_iters, damping, residual_tol,
+                    learn_rate, skip_gae, demo_coef, T_global, sub)
         want = self.graphs if graph is None else graph
         if want == "auto":
             # sharded: always (the graph holds the collectives too, no host launch
             # or collective-call overhead between the latency-bound steps)
-            want = T_all <= GRAPH_AUTO_ROWS or sharded
+            want = T_all <= GRAPH_AUTO_ROWS or self.sharded
         use_graph = (bool(want) and (self.comm.world_size == 1 or getattr(self.comm, "capturable", False))
                      and sub is None and algo in ("npg", "vpg", "dapg", "trpo"))
         if use_graph:
-            key = self._graph_key(batch, T_global, (algo, gamma, gae_lambda, n_step_size, const_lr, kl_dist, cg_iters,
-                                                    damping, residual_tol, learn_rate, skip_gae, demo_coef))
+            key = self._graph_key(u)
             gs = self._gstate
             if gs.get("graph") is not None and gs["key"] == key:
                 # replay: the whole update is one graph launch; theta enters through
@@ -1038,262 +1021,227 @@ class UpdateEngine:
                 self.last_T, self.last_T_global = T, T_global
                 trials = []
                 if algo == "trpo":   # the graph ends at the first evaluation; the search stays on the host
-                    trials = self._trpo_search(gs["plan"], gs["delta"], kl_dist, trpo_verbose, gs["timing"])
+                    trials = self._trpo_search(gs["plan"], gs["delta"], kl_dist, trpo_verbose, gs["timing"], st)
                 return self._finish(algo, const_lr, gs["delta"], T_global, None, trials, gs["timing"])
 
-        def launch(theta, ev):
-            """Every device launch of the update up to the first evaluation (the
-            TRPO line search continues on the host); `ev` makes timing events.
-            Under graph capture the current stream is the capture stream."""
-            st = _lib.stream_ptr()
-            self.st = st
-            timing = [ev() for _ in range(4)]
-
-            # a1-a3: returns / advantages.  The scan is a serial fp64 chain per path
-            # (latency-bound, few waves): it runs on a side stream beside the HBM-bound
-            # batch assembly and joins before the moments.
-            main = torch.cuda.current_stream(self.device)
-            side = self._side_stream()
-            self._baseline_of(batch)
-            side.wait_stream(main)
-            adv64 = w["adv64"]
-            if batch.advantages is not None:
-                adv64 = batch.advantages
-                # path returns still come from the rewards (npg_cg.py:97)
-                self.returns_advantages(batch, gamma, None, stream=C.c_void_p(side.cuda_stream))
-            elif not skip_gae:
-                self.returns_advantages(batch, gamma, gae_lambda, stream=C.c_void_p(side.cuda_stream))
-            # a5: batch assembly (f64 -> f32, input normalisation, bias column); fused
-            # into the forward pass below when it can be (_fused_pack): then only the
-            # column scales and the f32 actions here
-            fused = self._fused_pack(batch, T_all, T_all if (algo == "dapg" and demo_coef is not None) else T)
-            self._act_rows = None
-            if fused:
-                self._colscale(batch.obs, T_all, st, batch.obs_range)
-                if batch.act.dtype == torch.float32 and batch.act.is_contiguous() and tuple(batch.act.shape) == (
-                        T_all, s.m):
-                    # f32 staging: the row passes read the staged actions where they are
-                    # (a [T][m] copy into act32 cost ~30 us per 1M-row update)
-                    self._act_rows = batch.act
-                else:
-                    w["act32"][:T_all].copy_(batch.act[:T_all])
-            else:
-                self._pack(batch.obs, batch.act, T_all, st, batch.obs_range)
-            main.wait_stream(side)
-            # whitening (npg_cg.py:91) and path-return statistics (npg_cg.py:97-102):
-            # two-pass fp64 moments, both quantities in one launch per pass; when
-            # sharded, each pass's sums share one all-reduce (plus one MAX for the
-            # path-return extrema)
-            # (sharded: both passes local — pass 2 about this rank's own mean — then
-            # one all-gather of the four records and mjrl_moments_combine)
-            sp_ = lambda slot: C.c_void_p(self.stats[slot:].data_ptr())
-            mp2 = _lib.ptr(self.mom2_part)
-            dapg = algo == "dapg" and demo_coef is not None
-            _lib.check(L.mjrl_moments2(_lib.ptr(adv64), T, None, _lib.ptr(w["path_ret"]), P, None, mp2,
-                                       sp_(S_M1), sp_(S_PM1), st), "mjrl_moments2")
-            _lib.check(L.mjrl_moments2(_lib.ptr(adv64), T, sp_(S_M1), _lib.ptr(w["path_ret"]), P, sp_(S_PM1),
-                                       mp2, sp_(S_M2), sp_(S_PM2), st), "mjrl_moments2")
-            if sharded:
-                self._sharded_moments(S_M1, 32, 2, st)
-            # whitening + surr_before = mean(LR * adv) with LR == 1 (npg_cg.py:113) in one
-            # launch; the surr_before all-reduce rides with the first post-step evaluation's
-            _lib.check(L.mjrl_whiten_moments(_lib.ptr(adv64), T, sp_(S_M1), sp_(S_M2), 1e-6,
-                                             _lib.ptr(w["adv32"]), _lib.ptr(w["w64"]) if dapg else None, mp2,
-                                             sp_(S_MS), st), "mjrl_whiten_moments")
-            ms_pending = [True]
-            if dapg:
-                _lib.check(L.mjrl_moments2(_lib.ptr(w["w64"]), T, None, None, 0, None, mp2, sp_(S_MW1), None, st),
-                           "mjrl_moments2")
-                _lib.check(L.mjrl_moments2(_lib.ptr(w["w64"]), T, sp_(S_MW1), None, 0, None, mp2, sp_(S_MW2), None, st),
-                           "mjrl_moments2")
-                if sharded:
-                    self._sharded_moments(S_MW1, 16, 1, st)
-                _lib.check(L.mjrl_dapg_adv(_lib.ptr(w["w64"]), T, C.c_void_p(self.stats[S_MW1:].data_ptr()),
-                                           C.c_void_p(self.stats[S_MW2:].data_ptr()), T_demo, float(demo_coef),
-                                           _lib.ptr(w["adv_vpg"]), st), "mjrl_dapg_adv")
-                adv_vpg = w["adv_vpg"]
-                T_vpg = T_all
-            else:
-                adv_vpg = w["adv32"]
-                T_vpg = T
-            inv_T = 1.0 / T_global
-            self.last_T, self.last_T_global = T, T_global
-
-            # a6-a11: forward + VPG (caches a0, a1, mu0, ll0)
-            _lib.check(L.mjrl_pack_params(sp, _lib.ptr(theta), _lib.ptr(self.packed_theta), 1, self.min_log_std, st),
-                       "mjrl_pack_params")
-            sc = self._scratch(T_vpg)
-            rows = self._rows(T_vpg, adv_vpg)
-            timing[0].record()
-            if fused:
-                _lib.check(L.mjrl_policy_vpg_pack(sp, C.byref(rows), _lib.ptr(batch.obs), _lib.ptr(self.packed_theta),
-                                                  _lib.ptr(osh), _lib.ptr(osc), C.byref(sc), _lib.ptr(v["gsum"]), st),
-                           "mjrl_policy_vpg_pack")
-            else:
-                _lib.check(L.mjrl_policy_vpg(sp, C.byref(rows), _lib.ptr(self.packed_theta), _lib.ptr(osh),
-                                             _lib.ptr(osc), C.byref(sc), _lib.ptr(v["gsum"]), st), "mjrl_policy_vpg")
-            self.comm.allreduce_sum(v["gsum"])
-            if algo == "vpg":
-                _lib.check(L.mjrl_scale_vec(_lib.ptr(v["gsum"]), s.d, inv_T, _lib.ptr(v["g"]), st), "mjrl_scale_vec")
-            # (otherwise g = gsum / T is formed by the CG initialisation below, in the same launch)
-            timing[1].record()
-
-            # a12-a13: conjugate gradient with the device FVP
-            rows_fvp = self._rows(T, adv_vpg)
-            sc_fvp = self._scratch(T) if T_vpg != T else sc
-            if algo == "vpg":
-                x = v["g"]
-                cg_iters_run = 0
-            else:
-                _lib.check(L.mjrl_cg_init_scaled(sp, _lib.ptr(v["gsum"]), inv_T, _lib.ptr(v["g"]), _lib.ptr(v["x"]),
-                                                 _lib.ptr(v["r"]), _lib.ptr(v["p"]), _lib.ptr(self.packed_p),
-                                                 _lib.ptr(self.cg), _lib.ptr(self.done), st), "mjrl_cg_init_scaled")
-                prof = self.kernel_timing
-                inv_T_fvp = inv_T if sub is None else 1.0 / max(sub["Ts"], 1)
-                # gather + CG z fused when no all-reduce sits between them and the CG
-                # state holds one p.z partial per 64 parameters
-                cg_zx = (s.d + 63) // 64 <= (_lib.CG_STATE - _lib.CG_PZ_PARTS) // 2
-                fuse_cg = not sharded and cg_zx
-                for k in range(int(cg_iters)):
-                    rows_k, sc_k, T_k = rows_fvp, sc_fvp, T
-                    if sub is not None:
-                        rows_k, sc_k, T_k = self._subsample_rows(sub, k, adv_vpg)
-                    if prof is not None:
-                        e0, e1, e2 = (ev() for _ in range(3))
-                        e0.record()
-                    _lib.check(L.mjrl_fvp_accumulate(sp, C.byref(rows_k), T_k, _lib.ptr(self.packed_theta),
-                                                     _lib.ptr(self.packed_p), _lib.ptr(osc), _lib.ptr(self.done),
-                                                     C.byref(sc_k), st), "mjrl_fvp_accumulate")
-                    if prof is not None:
-                        e1.record()
-                    if fuse_cg:
-                        # one process: the slab gather and the z step of the CG iteration in one launch
-                        _lib.check(L.mjrl_gather_cg_z(sp, C.byref(rows_k), T_k, C.byref(sc_k), _lib.ptr(self.done),
-                                                      _lib.ptr(v["gsum"]), inv_T_fvp, float(damping),
-                                                      _lib.ptr(self.packed_theta), _lib.ptr(v["p"]), _lib.ptr(v["z"]),
-                                                      _lib.ptr(self.cg), st), "mjrl_gather_cg_z")
-                    else:
-                        _lib.check(L.mjrl_gather_grads(sp, C.byref(rows_k), T_k, C.byref(sc_k), 0, _lib.ptr(self.done),
-                                                       _lib.ptr(v["gsum"]), st), "mjrl_gather_grads")
-                    if prof is not None:
-                        e2.record()
-                        prof.append((e0, e1, e2))
-                    if fuse_cg:
-                        # the rest of the iteration in one launch; r alternates between two buffers
-                        r_in, r_out = (v["r"], v["r2"]) if k % 2 == 0 else (v["r2"], v["r"])
-                        _lib.check(L.mjrl_cg_step_xr_p(sp, _lib.ptr(v["x"]), _lib.ptr(r_in), _lib.ptr(r_out),
-                                                       _lib.ptr(v["p"]), _lib.ptr(v["z"]), _lib.ptr(self.packed_p),
-                                                       _lib.ptr(self.cg), _lib.ptr(self.done), float(residual_tol), st),
-                                   "mjrl_cg_step_xr_p")
-                        continue
-                    self.comm.allreduce_sum(v["gsum"])
-                    if cg_zx:
-                        # z + p.z partials from the reduced sum, then the one-process iteration tail
-                        _lib.check(L.mjrl_cg_z(sp, _lib.ptr(v["gsum"]), inv_T_fvp, float(damping),
-                                               _lib.ptr(self.packed_theta), _lib.ptr(v["p"]), _lib.ptr(v["z"]),
-                                               _lib.ptr(self.cg), _lib.ptr(self.done), st), "mjrl_cg_z")
-                        r_in, r_out = (v["r"], v["r2"]) if k % 2 == 0 else (v["r2"], v["r"])
-                        _lib.check(L.mjrl_cg_step_xr_p(sp, _lib.ptr(v["x"]), _lib.ptr(r_in), _lib.ptr(r_out),
-                                                       _lib.ptr(v["p"]), _lib.ptr(v["z"]), _lib.ptr(self.packed_p),
-                                                       _lib.ptr(self.cg), _lib.ptr(self.done), float(residual_tol),
-                                                       st), "mjrl_cg_step_xr_p")
-                        continue
-                    # the rest of the iteration in one launch; r and p alternate between two buffers each
-                    (r_in, r_out), (p_in, p_out) = ((v["r"], v["r2"]), (v["p"], v["p2"])) if k % 2 == 0 else \
-                        ((v["r2"], v["r"]), (v["p2"], v["p"]))
-                    _lib.check(L.mjrl_cg_step1(sp, _lib.ptr(v["gsum"]), inv_T_fvp, float(damping),
-                                               _lib.ptr(self.packed_theta), _lib.ptr(v["x"]), _lib.ptr(r_in),
-                                               _lib.ptr(r_out), _lib.ptr(p_in), _lib.ptr(p_out),
-                                               _lib.ptr(self.packed_p), _lib.ptr(self.cg), _lib.ptr(self.done),
-                                               float(residual_tol), st), "mjrl_cg_step1")
-                x = v["x"]
-                cg_iters_run = None
-            timing[2].record()
-
-            # a14: step size + update; a16 TRPO backtracking.  `plan` holds the
-            # buffers the step and the evaluation read (no reference to the engine:
-            # a captured graph keeps it for the TRPO search after each replay, and
-            # an engine <-> graph cycle would leave the graph's destruction to the
-            # cyclic GC, at any later allocation, possibly inside another capture)
-            plan = dict(x=x, theta=theta, rows=rows_fvp, sc=sc_fvp, T=T, osh=osh, osc=osc, ms_pending=[True],
-                        inv_T=inv_T)
-            if algo == "vpg":
-                self._step(plan, 1, 0.0, np.float32(learn_rate), 0)
-                delta = None
-            elif algo == "npg" and const_lr is not None:
-                self._step(plan, 1, 0.0, np.float32(const_lr), 1)
-                delta = None
-            elif algo == "npg":
-                delta = n_step_size if kl_dist is None else 2.0 * kl_dist
-                self._step(plan, 0, delta, 0.0, 0)
-            else:   # trpo / dapg: delta = 2 kl_dist
-                delta = 2.0 * kl_dist
-                self._step(plan, 0, delta, 0.0, 0)
-            self._evaluate(plan)
-            if algo == "trpo" and self.trpo_device_trials > 0 and not self.sharded:
-                # the first backtracking trials on the device (mjrl_trpo_trial): each
-                # tests the last evaluation and, rejected, steps to 0.9 alpha for the
-                # next; once one is accepted the rest return at once.  No host round
-                # trip per trial, and the whole sequence is part of the captured graph;
-                # the host continues past it only when all are rejected (_trpo_search)
-                K = int(self.trpo_device_trials)
-                for k in range(1, K + 2):
-                    _lib.check(L.mjrl_trpo_trial(sp, _lib.ptr(x), _lib.ptr(theta), self.min_log_std,
-                                                 _lib.ptr(v["theta_new"]), _lib.ptr(self.packed_new),
-                                                 _lib.ptr(self.out), C.c_void_p(self.stats[S_EVAL:].data_ptr()),
-                                                 inv_T, float(kl_dist), k, int(k <= K), _lib.ptr(self.ls_state),
-                                                 _lib.ptr(self.ls_skip), st), "mjrl_trpo_trial")
-                    if k <= K:
-                        self._evaluate(plan, skip=self.ls_skip)
-                plan["dev_trials"] = K
-            if algo != "trpo":
-                timing[3].record()
-            return plan, delta, timing
-
-        plan, delta, timing = launch(theta, lambda: torch.cuda.Event(enable_timing=True))
+        plan, delta, timing = self._launch(u, theta, lambda: torch.cuda.Event(enable_timing=True))
         trials = []
-
         if algo == "trpo":
-            trials = self._trpo_search(plan, delta, kl_dist, trpo_verbose, timing)
+            trials = self._trpo_search(plan, delta, kl_dist, trpo_verbose, timing, st)
         result = self._finish(algo, const_lr, delta, T_global, sub, trials, timing)
         if use_graph:
-            self._maybe_capture(key, launch, theta, delta, T_global)
+            self._maybe_capture(key, u, theta, delta)
         return result
 
-    def _step(self, plan, mode, delta, alpha_in, const):
+    def _launch(self, u, theta, ev):
+        """Every device launch of the update up to the first evaluation (the TRPO
+        line search continues on the host), as the stages of DESIGN.md §1's rows;
+        `ev` makes timing events.  The launch stream is the current one: under
+        graph capture, the capture stream."""
+        main = torch.cuda.current_stream(self.device)
+        st = C.c_void_p(main.cuda_stream)
+        timing = [ev() for _ in range(4)]
+        T = u.batch.T
+        fused, adv_vpg, T_vpg = self._stage_advantages(u, main, st)
+        self.last_T, self.last_T_global = T, u.T_global
+        # the rows / scratch of the forward pass (DAPG: the demonstration rows too)
+        # and of the FVPs and evaluations (the RL rows)
+        rows, sc = self._rows(T, adv_vpg), self._scratch(T)
+        rows_vpg, sc_vpg = (rows, sc) if T_vpg == T else (self._rows(T_vpg, adv_vpg), self._scratch(T_vpg))
+        self._stage_vpg(u, theta, fused, rows_vpg, sc_vpg, timing, st)
+        x = self.pvec["g"] if u.algo == "vpg" else self._stage_cg(u, rows, sc, adv_vpg, ev, st)
+        timing[2].record()
+        plan, delta = self._stage_step(u, theta, x, rows, sc, st)
+        if u.algo != "trpo":
+            timing[3].record()
+        return plan, delta, timing
+
+    def _stage_advantages(self, u, main, st):
+        """a1-a5: returns / advantages, batch assembly, moments, whitening, DAPG's
+        weights.  Returns (the forward pass assembles the rows itself, the f32
+        advantages the forward pass reads, its row count)."""
+        K, w, stats, batch = self.K, self.ws, self.stats, u.batch
+        T, T_all, P = batch.T, batch.T + batch.T_demo, batch.P
+        dapg = u.algo == "dapg" and u.demo_coef is not None
+        # a1-a3: returns / advantages.  The scan is a serial fp64 chain per path
+        # (latency-bound, few waves): it runs on a side stream beside the HBM-bound
+        # batch assembly and joins before the moments.
+        side = self._side_stream()
+        self._baseline_of(batch)
+        side.wait_stream(main)
+        adv64 = w["adv64"]
+        if batch.advantages is not None:
+            adv64 = batch.advantages
+            # path returns still come from the rewards (npg_cg.py:97)
+            self.returns_advantages(batch, u.gamma, None, stream=C.c_void_p(side.cuda_stream))
+        elif not u.skip_gae:
+            self.returns_advantages(batch, u.gamma, u.gae_lambda, stream=C.c_void_p(side.cuda_stream))
+        # a5: batch assembly (f64 -> f32, input normalisation, bias column); fused
+        # into the forward pass when it can be (_fused_pack): then only the column
+        # scales and the f32 actions here
+        fused = self._fused_pack(batch, T_all, T_all if dapg else T)
+        self._act_rows = None
+        if fused:
+            self._colscale(batch.obs, T_all, st, batch.obs_range)
+            if batch.act.dtype == torch.float32 and batch.act.is_contiguous() and tuple(batch.act.shape) == (
+                    T_all, self.shape.m):
+                # f32 staging: the row passes read the staged actions where they are
+                # (a [T][m] copy into act32 cost ~30 us per 1M-row update)
+                self._act_rows = batch.act
+            else:
+                w["act32"][:T_all].copy_(batch.act[:T_all])
+        else:
+            self._pack(batch.obs, batch.act, T_all, st, batch.obs_range)
+        main.wait_stream(side)
+        # whitening (npg_cg.py:91) and path-return statistics (npg_cg.py:97-102):
+        # two-pass fp64 moments, both quantities in one launch per pass (sharded:
+        # both passes local — pass 2 about this rank's own mean — then one
+        # all-gather of the four records and mjrl_moments_combine)
+        mp2, pr = self.mom2_part, w["path_ret"]
+        K.mjrl_moments2(adv64, T, None, pr, P, None, mp2, stats[S_M1:], stats[S_PM1:], st)
+        K.mjrl_moments2(adv64, T, stats[S_M1:], pr, P, stats[S_PM1:], mp2, stats[S_M2:], stats[S_PM2:], st)
+        if self.sharded:
+            self._sharded_moments(S_M1, 32, 2, st)
+        # whitening + surr_before = mean(LR * adv) with LR == 1 (npg_cg.py:113) in one
+        # launch; the surr_before all-reduce rides with the first post-step evaluation's
+        K.mjrl_whiten_moments(adv64, T, stats[S_M1:], stats[S_M2:], 1e-6, w["adv32"], w["w64"] if dapg else None,
+                              mp2, stats[S_MS:], st)
+        if not dapg:
+            return fused, w["adv32"], T
+        K.mjrl_moments2(w["w64"], T, None, None, 0, None, mp2, stats[S_MW1:], None, st)
+        K.mjrl_moments2(w["w64"], T, stats[S_MW1:], None, 0, None, mp2, stats[S_MW2:], None, st)
+        if self.sharded:
+            self._sharded_moments(S_MW1, 16, 1, st)
+        K.mjrl_dapg_adv(w["w64"], T, stats[S_MW1:], stats[S_MW2:], batch.T_demo, float(u.demo_coef), w["adv_vpg"], st)
+        return fused, w["adv_vpg"], T_all
+
+    def _stage_vpg(self, u, theta, fused, rows, sc, timing, st):
+        """a6-a11: forward + VPG sums over `rows` (caches a0, a1, mu0, ll0), all-reduced."""
+        K, s, gsum = self.K, self.shape, self.pvec["gsum"]
+        _, _, osh, osc = self.transforms
+        K.mjrl_pack_params(s, theta, self.packed_theta, 1, self.min_log_std, st)
+        timing[0].record()
+        if fused:
+            K.mjrl_policy_vpg_pack(s, rows, u.batch.obs, self.packed_theta, osh, osc, sc, gsum, st)
+        else:
+            K.mjrl_policy_vpg(s, rows, self.packed_theta, osh, osc, sc, gsum, st)
+        self.comm.allreduce_sum(gsum)
+        if u.algo == "vpg":
+            K.mjrl_scale_vec(gsum, s.d, 1.0 / u.T_global, self.pvec["g"], st)
+        # (otherwise g = gsum / T is formed by the CG initialisation, in the same launch)
+        timing[1].record()
+
+    def _stage_cg(self, u, rows, sc, adv_vpg, ev, st):
+        """a12-a13: conjugate gradient with the device FVP; returns x.  An
+        iteration is accumulate, gather, then one of three schedules, chosen once:
+        'gather_z' (one process, one p.z partial per 64 parameters fits the CG
+        state): the gather fused with the z step, then the tail; 'z' (sharded):
+        all-reduce, mjrl_cg_z, the same tail; 'step1' (more partials than the
+        state holds): all-reduce, then the rest of the iteration in mjrl_cg_step1."""
+        K, s, v, sub = self.K, self.shape, self.pvec, u.sub
+        osc = self.transforms[3]
+        inv_T = 1.0 / u.T_global
+        K.mjrl_cg_init_scaled(s, v["gsum"], inv_T, v["g"], v["x"], v["r"], v["p"], self.packed_p, self.cg, self.done,
+                              st)
+        prof = self.kernel_timing
+        inv_T_fvp = inv_T if sub is None else 1.0 / max(sub["Ts"], 1)
+        damping, tol = float(u.damping), float(u.residual_tol)
+        if (s.d + 63) // 64 > (_lib.CG_STATE - _lib.CG_PZ_PARTS) // 2:
+            schedule = "step1"
+        else:
+            schedule = "z" if self.sharded else "gather_z"
+        rows_k, sc_k, T_k = rows, sc, u.batch.T
+        for k in range(int(u.cg_iters)):
+            if sub is not None:
+                rows_k, sc_k, T_k = self._subsample_rows(sub, k, adv_vpg, st)
+            if prof is not None:
+                e0, e1, e2 = (ev() for _ in range(3))
+                e0.record()
+            K.mjrl_fvp_accumulate(s, rows_k, T_k, self.packed_theta, self.packed_p, osc, self.done, sc_k, st)
+            if prof is not None:
+                e1.record()
+            if schedule == "gather_z":
+                K.mjrl_gather_cg_z(s, rows_k, T_k, sc_k, self.done, v["gsum"], inv_T_fvp, damping, self.packed_theta,
+                                   v["p"], v["z"], self.cg, st)
+            else:
+                K.mjrl_gather_grads(s, rows_k, T_k, sc_k, 0, self.done, v["gsum"], st)
+            if prof is not None:
+                e2.record()
+                prof.append((e0, e1, e2))
+            if schedule != "gather_z":
+                self.comm.allreduce_sum(v["gsum"])
+            if schedule == "z":   # z + p.z partials from the reduced sum
+                K.mjrl_cg_z(s, v["gsum"], inv_T_fvp, damping, self.packed_theta, v["p"], v["z"], self.cg, self.done, st)
+            # the rest of the iteration in one launch: r (step1: p too) alternates between two buffers
+            r_in, r_out = (v["r"], v["r2"]) if k % 2 == 0 else (v["r2"], v["r"])
+            if schedule == "step1":
+                p_in, p_out = (v["p"], v["p2"]) if k % 2 == 0 else (v["p2"], v["p"])
+                K.mjrl_cg_step1(s, v["gsum"], inv_T_fvp, damping, self.packed_theta, v["x"], r_in, r_out, p_in, p_out,
+                                self.packed_p, self.cg, self.done, tol, st)
+            else:
+                K.mjrl_cg_step_xr_p(s, v["x"], r_in, r_out, v["p"], v["z"], self.packed_p, self.cg, self.done, tol, st)
+        return v["x"]
+
+    def _stage_step(self, u, theta, x, rows, sc, st):
+        """a14: step size + update, the first evaluation, and (a16) TRPO's first
+        backtracking trials on the device.  Returns (plan, delta).  `plan` holds
+        the buffers the step and the evaluation read (no reference to the engine:
+        a captured graph keeps it for the TRPO search after each replay, and an
+        engine <-> graph cycle would leave the graph's destruction to the cyclic
+        GC, at any later allocation, possibly inside another capture)."""
+        _, _, osh, osc = self.transforms
+        inv_T = 1.0 / u.T_global
+        plan = dict(x=x, theta=theta, rows=rows, sc=sc, T=u.batch.T, osh=osh, osc=osc, ms_pending=[True], inv_T=inv_T)
+        delta = None
+        if u.algo == "vpg":
+            self._step(plan, 1, 0.0, np.float32(u.learn_rate), 0, st)
+        elif u.algo == "npg" and u.const_lr is not None:
+            self._step(plan, 1, 0.0, np.float32(u.const_lr), 1, st)
+        else:   # npg: delta = n_step_size unless kl_dist is given; trpo / dapg: delta = 2 kl_dist
+            delta = u.n_step_size if (u.algo == "npg" and u.kl_dist is None) else 2.0 * u.kl_dist
+            self._step(plan, 0, delta, 0.0, 0, st)
+        self._evaluate(plan, st)
+        if u.algo == "trpo" and self.trpo_device_trials > 0 and not self.sharded:
+            # the first backtracking trials on the device (mjrl_trpo_trial): each
+            # tests the last evaluation and, rejected, steps to 0.9 alpha for the
+            # next; once one is accepted the rest return at once.  No host round
+            # trip per trial, and the whole sequence is part of the captured graph;
+            # the host continues past it only when all are rejected (_trpo_search)
+            n_dev = int(self.trpo_device_trials)
+            for k in range(1, n_dev + 2):
+                self.K.mjrl_trpo_trial(self.shape, x, theta, self.min_log_std, self.pvec["theta_new"], self.packed_new,
+                                       self.out, self.stats[S_EVAL:], inv_T, float(u.kl_dist), k, int(k <= n_dev),
+                                       self.ls_state, self.ls_skip, st)
+                if k <= n_dev:
+                    self._evaluate(plan, st, skip=self.ls_skip)
+            plan["dev_trials"] = n_dev
+        return plan, delta
+
+    def _step(self, plan, mode, delta, alpha_in, const, st):
         """a14: theta_new = theta + alpha x (npg_cg.py:128-141), alpha from the
         step-size rule (mode 0) or given (mode 1), log-std clamp, repack."""
-        L = self.lib
-        _lib.check(L.mjrl_npg_step(C.byref(self.shape), _lib.ptr(self.pvec["g"]), _lib.ptr(plan["x"]),
-                                   _lib.ptr(plan["theta"]), mode, float(delta), float(alpha_in), int(const),
-                                   self.min_log_std, _lib.ptr(self.pvec["theta_new"]), _lib.ptr(self.packed_new),
-                                   _lib.ptr(self.out), _lib.stream_ptr()), "mjrl_npg_step")
+        self.K.mjrl_npg_step(self.shape, self.pvec["g"], plan["x"], plan["theta"], mode, float(delta), float(alpha_in),
+                             int(const), self.min_log_std, self.pvec["theta_new"], self.packed_new, self.out, st)
 
-    def _evaluate(self, plan, skip=None):
+    def _evaluate(self, plan, st, skip=None):
         """Surrogate and KL at theta_new (npg_cg.py:142-143): one EVAL pass, then
         (sharded) the all-reduce of its sums; the first one carries surr_before's
         moments too.  skip: a device flag that turns the pass into a no-op (the
         device line search's speculative evaluations; one process only)."""
-        L = self.lib
+        K = self.K
         if skip is not None:
-            _lib.check(L.mjrl_policy_eval_if(C.byref(self.shape), C.byref(plan["rows"]), plan["T"],
-                                             _lib.ptr(self.packed_new), _lib.ptr(self.packed_theta),
-                                             _lib.ptr(plan["osh"]), _lib.ptr(plan["osc"]), C.byref(plan["sc"]),
-                                             C.c_void_p(self.stats[S_EVAL:].data_ptr()), _lib.ptr(skip),
-                                             _lib.stream_ptr()), "mjrl_policy_eval_if")
+            K.mjrl_policy_eval_if(self.shape, plan["rows"], plan["T"], self.packed_new, self.packed_theta, plan["osh"],
+                                  plan["osc"], plan["sc"], self.stats[S_EVAL:], skip, st)
             return
-        _lib.check(L.mjrl_policy_eval(C.byref(self.shape), C.byref(plan["rows"]), plan["T"],
-                                      _lib.ptr(self.packed_new), _lib.ptr(self.packed_theta), _lib.ptr(plan["osh"]),
-                                      _lib.ptr(plan["osc"]), C.byref(plan["sc"]),
-                                      C.c_void_p(self.stats[S_EVAL:].data_ptr()), _lib.stream_ptr()),
-                   "mjrl_policy_eval")
+        K.mjrl_policy_eval(self.shape, plan["rows"], plan["T"], self.packed_new, self.packed_theta, plan["osh"],
+                           plan["osc"], plan["sc"], self.stats[S_EVAL:], st)
         if plan["ms_pending"][0]:
             self._reduce_stats(S_MS, S_EVAL + 2)   # surr_before's moments + the eval sums
             plan["ms_pending"][0] = False
         else:
             self._reduce_stats(S_EVAL, S_EVAL + 2)
 
-    def _trpo_search(self, plan, delta, kl_dist, verbose, timing):
+    def _trpo_search(self, plan, delta, kl_dist, verbose, timing, st):
         """TRPO's KL backtracking (trpo.py:98-124) after the first evaluation: alpha
         *= 0.9 while KL >= kl_dist (at most 100 trials), then the final
         re-evaluation at the accepted alpha.  The first trpo_device_trials trials
@@ -1324,8 +1272,8 @@ class UpdateEngine:
                 return trials
             # every device trial rejected: the host steps on from the last one
             alpha = np.float32(0.9 * np.float32(trials[-1][0]))   # trpo.py:114 (python float * np.float32)
-            self._step(plan, 1, delta, alpha, 0)
-            self._evaluate(plan)
+            self._step(plan, 1, delta, alpha, 0, st)
+            self._evaluate(plan, st)
             k0 = n
         else:
             alpha = np.float32(self.out[0].item())
@@ -1341,12 +1289,12 @@ class UpdateEngine:
             if k == 99:
                 alpha = np.float32(0.0)
                 break
-            self._step(plan, 1, delta, alpha, 0)
-            self._evaluate(plan)
+            self._step(plan, 1, delta, alpha, 0, st)
+            self._evaluate(plan, st)
             res = self.stats[S_EVAL:S_EVAL + 2].cpu().numpy()
         if float(alpha) != trials[-1][0]:   # final re-evaluation (trpo.py:120-123)
-            self._step(plan, 1, delta, alpha, 0)
-            self._evaluate(plan)
+            self._step(plan, 1, delta, alpha, 0, st)
+            self._evaluate(plan, st)
         timing[3].record()
         return trials
 
@@ -1357,14 +1305,16 @@ class UpdateEngine:
     # then cost no host time and leave no launch gaps).  Theta enters through a
     # captured device buffer; everything else the graph reads is the batch and
     # the engine workspace, whose addresses are part of the key.
-    def _graph_key(self, batch, T_global, args):
+    def _graph_key(self, u):
+        batch = u.batch
         ptrs = tuple(0 if t is None else t.data_ptr() for t in (
             batch.obs, batch.act, batch.rewards, batch.baseline, batch.path_off, batch.terminated, batch.advantages,
             batch.obs_range) + tuple(self.transforms))
-        return (ptrs, batch.T, batch.T_demo, batch.P, float(T_global), self._ws_gen, self.kernel_timing is not None,
-                tuple(args))
+        # u[1:-2]: every argument of the update (not the batch, T_global, the absent subsample)
+        return (ptrs, batch.T, batch.T_demo, batch.P, float(u.T_global), self._ws_gen, self.kernel_timing is not None,
+                tuple(u[1:-2]))
 
-    def _maybe_capture(self, key, launch, theta, delta, T_global):
+    def _maybe_capture(self, key, u, theta, delta):
         gs = self._gstate
         if gs.get("seen") != key:          # first sighting: remember, stay eager
             gs.clear()
@@ -1379,22 +1329,20 @@ class UpdateEngine:
             g = torch.cuda.CUDAGraph()
             try:
                 with capture(g):
-                    out = launch(theta_in, ev)
+                    out = self._launch(u, theta_in, ev)
             except Exception as e:         # timing events inside a capture unsupported: capture without
                 err = e
                 continue
             finally:
                 graph_prof = self.kernel_timing
                 self.kernel_timing = prof_saved
-            # plan: buffers only (no closure over the engine, see launch())
+            # plan: buffers only (no reference to the engine or to `u`, see _stage_step)
             gs.update(key=key, graph=g, theta_in=theta_in, timing=out[2], delta=delta, prof=graph_prof, plan=out[0])
-            self.st = _lib.stream_ptr()    # launch() cached the capture stream
             return
         import warnings
         warnings.warn("mjrl_amd: hipGraph capture of the update failed (%s); staying eager" % (err,))
         self.graphs = False
         gs.clear()
-        self.st = _lib.stream_ptr()
 
     def graph_kernel_timing(self):
         """(start, accumulate done, gather done) external events of every FVP of the
@@ -1466,15 +1414,14 @@ class UpdateEngine:
         computed from device residuals as the reference does.  obs_lo: the low
         halves of f32-staged observations (DeviceBatch.obs_lo): the features are
         then formed from hi + lo, the sampler's f64 values to 2^-48."""
-        L = self.lib
+        K = self.K
         st = _lib.stream_ptr()
         n, T, P = int(batch.obs.shape[1]), batch.T, batch.P
         k = n + n * (n + 1) // 2 + 5 if quadratic else n + 4
         y = returns if returns is not None else self.ws["ret"][:T]
         nd = C.c_int64()
         kind = "quadratic" if quadratic else "linear"
-        _lib.check(getattr(L, "mjrl_%s_baseline_gram_scratch" % kind)(n, T, C.byref(nd)),
-                   "mjrl_%s_baseline_gram_scratch" % kind)
+        getattr(K, "mjrl_%s_baseline_gram_scratch" % kind)(n, T, nd)
         f64 = dict(dtype=torch.float64, device=self.device)
         scratch = torch.empty(max(nd.value, 1), **f64)
         gram = torch.zeros((k + 1, k + 1), **f64)
@@ -1482,34 +1429,27 @@ class UpdateEngine:
         if obs_lo is not None and f32:
             if obs_lo.dtype != torch.float32 or obs_lo.shape[0] < T or obs_lo.shape[1] != n:
                 raise ValueError("fit_%s_baseline: obs_lo must be float32 [T, n]" % kind)
-        if quadratic and f32:   # one f32 entry, low halves or null
-            lo = _lib.ptr(obs_lo) if obs_lo is not None else None
-            gram_fn = functools.partial(L.mjrl_quadratic_baseline_gram_f32, _lib.ptr(batch.obs))
-            res_fn = functools.partial(L.mjrl_quadratic_baseline_residual_f32, _lib.ptr(batch.obs))
-            obs_arg = lo
-        elif quadratic:
-            gram_fn, res_fn = L.mjrl_quadratic_baseline_gram, L.mjrl_quadratic_baseline_residual
-            obs_arg = _lib.ptr(batch.obs)
-        elif f32 and obs_lo is not None:
-            gram_fn = functools.partial(L.mjrl_linear_baseline_gram_f32x2, _lib.ptr(batch.obs))
-            res_fn = functools.partial(L.mjrl_linear_baseline_residual_f32x2, _lib.ptr(batch.obs))
-            obs_arg = _lib.ptr(obs_lo)
-        else:
-            gram_fn = L.mjrl_linear_baseline_gram_f32 if f32 else L.mjrl_linear_baseline_gram
-            res_fn = L.mjrl_linear_baseline_residual_f32 if f32 else L.mjrl_linear_baseline_residual
-            obs_arg = _lib.ptr(batch.obs)
-        _lib.check(gram_fn(obs_arg, _lib.ptr(y), T, n, _lib.ptr(batch.path_off), P,
-                           _lib.ptr(scratch), _lib.ptr(gram), st), "mjrl_%s_baseline_gram" % kind)
+        # (quadratic, f32 observations, their low halves given) -> the suffix of the
+        # gram / residual entry points and whether they take (obs, obs_lo) or obs alone;
+        # the quadratic f32 entry is one, with low halves or null
+        has_lo = f32 and obs_lo is not None
+        suffix, pair = {(False, False, False): ("", False), (False, True, False): ("_f32", False),
+                        (False, True, True): ("_f32x2", True), (True, False, False): ("", False),
+                        (True, True, False): ("_f32", True), (True, True, True): ("_f32", True)}[
+            (bool(quadratic), f32, has_lo)]
+        gram_fn = getattr(K, "mjrl_%s_baseline_gram%s" % (kind, suffix))
+        res_fn = getattr(K, "mjrl_%s_baseline_residual%s" % (kind, suffix))
+        obs_args = (batch.obs, obs_lo if has_lo else None) if pair else (batch.obs,)
+        gram_fn(*obs_args, y, T, n, batch.path_off, P, scratch, gram, st)
         self.comm.allreduce_sum(gram)
 
         def sse(coeffs):
             r = torch.empty(max(T, 1), **f64)
             c = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64)).to(self.device)
-            _lib.check(res_fn(obs_arg, _lib.ptr(y), T, n, _lib.ptr(batch.path_off), P, _lib.ptr(c),
-                              _lib.ptr(scratch), _lib.ptr(r), st), "mjrl_%s_baseline_residual" % kind)
+            res_fn(*obs_args, y, T, n, batch.path_off, P, c, scratch, r, st)
             out = torch.zeros(8, **f64)
             part = torch.empty(4 * 256, **f64)
-            _lib.check(L.mjrl_moments(_lib.ptr(r), T, None, _lib.ptr(part), _lib.ptr(out), st), "mjrl_moments")
+            K.mjrl_moments(r, T, None, part, out, st)
             self.comm.allreduce_sum(out)
             return float(out[1].item())
 
@@ -1553,9 +1493,9 @@ class UpdateEngine:
         mx = int(counts.max()) if K else 0
         return dict(idx=loc, counts=counts, offs=offs, Ts=Ts, N=N, rng=rng, max=mx)
 
-    def _subsample_rows(self, sub, k, adv_vpg):
-        """Compact xhat / a0 / a1 rows of draw k (mjrl_gather_rows) and the Rows /
-        Scratch an FVP over them uses."""
+    def _subsample_rows(self, sub, k, adv_vpg, st):
+        """Compact xhat / a0 / a1 rows of draw k (mjrl_gather_rows, on stream st)
+        and the Rows / Scratch an FVP over them uses."""
         s = self.shape
         n_k = int(sub["counts"][k])
         ip = C.c_void_p(sub["idx"].data_ptr() + 8 * int(sub["offs"][k]))
@@ -1564,11 +1504,9 @@ class UpdateEngine:
         f32 = dict(dtype=torch.float32, device=self.device)
         ws = self.__dict__.setdefault("ws_sub", {})
         if "a0s" not in ws or ws["a0s"].shape[0] < cap:
-            wf, rd, sl = C.c_int64(), C.c_int64(), C.c_int32()
-            _lib.check(self.lib.mjrl_scratch_size(C.byref(s), cap, C.byref(wf), C.byref(rd), C.byref(sl)),
-                       "mjrl_scratch_size")
-            ws["wpart"] = torch.empty(max(wf.value, 1), **f32)
-            ws["rpart"] = torch.zeros(max(rd.value, 1), dtype=torch.float64, device=self.device)
+            wf, rd, _ = self._scratch_size(cap)
+            ws["wpart"] = torch.empty(max(wf, 1), **f32)
+            ws["rpart"] = torch.zeros(max(rd, 1), dtype=torch.float64, device=self.device)
             if self.split:
                 ws["xss"] = torch.empty((cap, 2 * s.np), dtype=torch.float16, device=self.device)
                 ws["xus"] = torch.empty(cap, **f32)
@@ -1585,8 +1523,7 @@ class UpdateEngine:
             pairs += [("a0", "a0s", s.h0), ("a1", "a1s", s.h1)]
         rows = self._rows(n_k, adv_vpg)
         for src, dst, width in pairs:   # rows of 4 * width bytes (f32, or the f16 hi / lo pair of xs)
-            _lib.check(self.lib.mjrl_gather_rows(_lib.ptr(w[src]), 4 * width, ip, n_k, _lib.ptr(ws[dst]), self.st),
-                       "mjrl_gather_rows")
+            self.K.mjrl_gather_rows(w[src], 4 * width, ip, n_k, ws[dst], st)
             setattr(rows, src, ws[dst].data_ptr())
         rows.gu0, rows.gu1, rows.gp = ws["gu0s"].data_ptr(), ws["gu1s"].data_ptr(), ws["gps"].data_ptr()
         return rows, self._scratch(n_k, ws), n_k
@@ -1594,7 +1531,7 @@ class UpdateEngine:
     def accumulate_path(self):
         """Accumulate kernel the dispatcher runs for this shape: 2 = K-split
         persistent (k_ks), 1 = fused persistent (k_fused), 0 = k_rows + k_wgrad."""
-        return int(self.lib.mjrl_fused_path(C.byref(self.shape)))
+        return int(self.K.mjrl_fused_path(self.shape))
 
     @_on_device
     def fvp(self, v, damping=1e-4, T=None, idx=None):
@@ -1604,32 +1541,26 @@ class UpdateEngine:
         `NPG.HVP`.  `v`: f32 device tensor [d].  `idx` (int64 device tensor):
         the rows of a subsampled Fisher (npg_cg.py:58-62), gathered as in the
         update's CG loop.  Returns a new device tensor."""
-        L = self.lib
-        s = self.shape
-        sp = C.byref(s)
-        self.st = st = _lib.stream_ptr()
+        K, s = self.K, self.shape
+        st = _lib.stream_ptr()
         T = self.last_T if T is None else T
         vv = self.pvec
         T_global = self.last_T_global
         if idx is not None:
             n = int(idx.numel())
             sub = dict(idx=idx.contiguous(), counts=[n], offs=[0], max=n)
-            rows, scratch, T = self._subsample_rows(sub, 0, self.ws["adv32"])
+            rows, scratch, T = self._subsample_rows(sub, 0, self.ws["adv32"], st)
             T_global = float(n)
         else:
             scratch = self._scratch(T)
             rows = self._rows(T, self.ws["adv32"])
         v = self._pad(v, "v")
-        _lib.check(L.mjrl_cg_init(sp, _lib.ptr(v), _lib.ptr(vv["x"]), _lib.ptr(vv["r"]), _lib.ptr(vv["p"]),
-                                  _lib.ptr(self.packed_p), _lib.ptr(self.cg), _lib.ptr(self.done), st), "mjrl_cg_init")
-        _lib.check(L.mjrl_policy_fvp(sp, C.byref(rows), T, _lib.ptr(self.packed_theta), _lib.ptr(self.packed_p),
-                                     _lib.ptr(self.transforms[3]), C.byref(scratch), _lib.ptr(self.done),
-                                     _lib.ptr(vv["gsum"]), st), "mjrl_policy_fvp")
+        K.mjrl_cg_init(s, v, vv["x"], vv["r"], vv["p"], self.packed_p, self.cg, self.done, st)
+        K.mjrl_policy_fvp(s, rows, T, self.packed_theta, self.packed_p, self.transforms[3], scratch, self.done,
+                          vv["gsum"], st)
         self.comm.allreduce_sum(vv["gsum"])
-        _lib.check(L.mjrl_cg_step(sp, _lib.ptr(vv["gsum"]), 1.0 / T_global, float(damping),
-                                  _lib.ptr(self.packed_theta), _lib.ptr(vv["x"]), _lib.ptr(vv["r"]), _lib.ptr(vv["p"]),
-                                  _lib.ptr(vv["z"]), _lib.ptr(self.packed_p), _lib.ptr(self.cg), _lib.ptr(self.done),
-                                  0.0, st), "mjrl_cg_step")
+        K.mjrl_cg_step(s, vv["gsum"], 1.0 / T_global, float(damping), self.packed_theta, vv["x"], vv["r"], vv["p"],
+                       vv["z"], self.packed_p, self.cg, self.done, 0.0, st)
         return self._unpad(vv["z"]).clone()
 
     # ------------------------------------------------------------------
@@ -1644,12 +1575,10 @@ class UpdateEngine:
         T = int(obs.shape[0])
         self._ensure(T, 1)
         self._act_rows = None   # the rows' actions are act32's from here on
-        self.st = st = _lib.stream_ptr()
         dev = self.device
         o = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float64)).to(dev)
         a = torch.from_numpy(np.ascontiguousarray(act, dtype=np.float64)).to(dev)
-        ins, isc, _, _ = self.transforms
-        self._pack(o, a, T, st)
+        self._pack(o, a, T, _lib.stream_ptr())
         if adv is not None:
             self.ws["adv32"][:T].copy_(torch.from_numpy(np.asarray(adv, dtype=np.float64)).float().to(dev))
         else:
@@ -1660,38 +1589,28 @@ class UpdateEngine:
     def forward_pass(self, theta, T):
         """Forward + VPG sums at theta over the loaded rows; fills the caches.
         Returns the flat VPG mean (device) = sum / T."""
-        L, s = self.lib, self.shape
+        K, s = self.K, self.shape
         theta = self._pad(theta, "theta")
-        sp = C.byref(s)
-        self.st = st = _lib.stream_ptr()
-        _lib.check(L.mjrl_pack_params(sp, _lib.ptr(theta), _lib.ptr(self.packed_theta), 1, self.min_log_std, st),
-                   "mjrl_pack_params")
-        rows = self._rows(T, self.ws["adv32"])
-        sc = self._scratch(T)
+        st = _lib.stream_ptr()
+        K.mjrl_pack_params(s, theta, self.packed_theta, 1, self.min_log_std, st)
         _, _, osh, osc = self.transforms
-        _lib.check(L.mjrl_policy_vpg(sp, C.byref(rows), _lib.ptr(self.packed_theta), _lib.ptr(osh), _lib.ptr(osc),
-                                     C.byref(sc), _lib.ptr(self.pvec["gsum"]), st), "mjrl_policy_vpg")
+        K.mjrl_policy_vpg(s, self._rows(T, self.ws["adv32"]), self.packed_theta, osh, osc, self._scratch(T),
+                          self.pvec["gsum"], st)
         tg = float(T)
         self.last_T, self.last_T_global = T, tg
-        _lib.check(L.mjrl_scale_vec(_lib.ptr(self.pvec["gsum"]), s.d, 1.0 / tg, _lib.ptr(self.pvec["g"]), st),
-                   "mjrl_scale_vec")
+        K.mjrl_scale_vec(self.pvec["gsum"], s.d, 1.0 / tg, self.pvec["g"], st)
         return self._unpad(self.pvec["g"])
 
     @_on_device
     def eval_pass(self, theta_new, T):
         """(surrogate, KL) at theta_new against the caches of the last forward_pass."""
-        L, s = self.lib, self.shape
+        K, s = self.K, self.shape
         theta_new = self._pad(theta_new, "theta_new")
-        sp = C.byref(s)
-        self.st = st = _lib.stream_ptr()
-        _lib.check(L.mjrl_pack_params(sp, _lib.ptr(theta_new), _lib.ptr(self.packed_new), 1, self.min_log_std, st),
-                   "mjrl_pack_params")
-        rows = self._rows(T, self.ws["adv32"])
-        sc = self._scratch(T)
+        st = _lib.stream_ptr()
+        K.mjrl_pack_params(s, theta_new, self.packed_new, 1, self.min_log_std, st)
         _, _, osh, osc = self.transforms
-        _lib.check(L.mjrl_policy_eval(sp, C.byref(rows), T, _lib.ptr(self.packed_new), _lib.ptr(self.packed_theta),
-                                      _lib.ptr(osh), _lib.ptr(osc), C.byref(sc),
-                                      C.c_void_p(self.stats[S_EVAL:].data_ptr()), st), "mjrl_policy_eval")
+        K.mjrl_policy_eval(s, self._rows(T, self.ws["adv32"]), T, self.packed_new, self.packed_theta, osh, osc,
+                           self._scratch(T), self.stats[S_EVAL:], st)
         res = self.stats[S_EVAL:S_EVAL + 2].cpu().numpy()
         return np.float32(res[0] / T), np.float32(res[1] / T)
 
@@ -1702,7 +1621,7 @@ def device_returns_advantages(rewards, baseline, lengths, terminated, gamma, gae
     host arrays; returns f64 numpy (returns, advantages), bit-identical to the
     reference's discount_sum order.  normalize: (adv - mean) / (std + 1e-8) over
     all paths (process_samples.py:14-19, 30-35), two-pass fp64 moments."""
-    L = _lib.lib()
+    K = _lib.calls()
     dev = torch.device(device if device is not None else "cuda")
     lengths = np.asarray(lengths, dtype=np.int64)
     T = int(lengths.sum())
@@ -1716,18 +1635,13 @@ def device_returns_advantages(rewards, baseline, lengths, terminated, gamma, gae
     ret = torch.empty(max(T, 1), dtype=torch.float64, device=dev)
     adv = torch.empty(max(T, 1), dtype=torch.float64, device=dev)
     pr = torch.empty(max(P, 1), dtype=torch.float64, device=dev)
-    _lib.check(L.mjrl_gae(_lib.ptr(rw), _lib.ptr(bl), _lib.ptr(off), _lib.ptr(term), P, float(gamma),
-                          float(gae_lambda) if use_gae else 0.0, int(use_gae), _lib.ptr(ret), _lib.ptr(adv),
-                          _lib.ptr(pr), _lib.stream_ptr()), "mjrl_gae")
+    st = _lib.stream_ptr()
+    K.mjrl_gae(rw, bl, off, term, P, float(gamma), float(gae_lambda) if use_gae else 0.0, int(use_gae), ret, adv, pr,
+               st)
     if normalize and T > 0:
-        st = _lib.stream_ptr()
         part = torch.zeros(4 * 256 + 16, dtype=torch.float64, device=dev)
         m = torch.zeros(16, dtype=torch.float64, device=dev)
         out = torch.empty(T, dtype=torch.float64, device=dev)
-        _lib.check(L.mjrl_moments(_lib.ptr(adv), T, None, _lib.ptr(part), _lib.ptr(m), st), "mjrl_moments")
-        _lib.check(L.mjrl_moments(_lib.ptr(adv), T, _lib.ptr(m), _lib.ptr(part), C.c_void_p(m[8:].data_ptr()), st),
-                   "mjrl_moments")
-        _lib.check(L.mjrl_whiten(_lib.ptr(adv), T, _lib.ptr(m), C.c_void_p(m[8:].data_ptr()), 1e-8, None,
-                                 _lib.ptr(out), st), "mjrl_whiten")
+        _normalize(K, adv, T, part, m, m[8:], out, st)
         adv = out
     return ret[:T].cpu().numpy(), adv[:T].cpu().numpy()

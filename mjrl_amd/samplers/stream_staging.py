@@ -62,7 +62,7 @@ class StreamSink:
         c = _linear_coeffs(baseline, self.n)
         self.linear = c is not False
         self.coeffs = None if c is False or c is None else np.ascontiguousarray(c, dtype=np.float64)
-        self.L = _lib.stage_lib()
+        self.S = _lib.stage_calls()
         S, B, H = int(nslots), self.NBUF, self.H
         # pinned per-slot slabs, [slot][buf][H][n] f32 observations, [..][m] actions
         # and [..] f64 predictions, kept across batches (a training loop builds one
@@ -124,10 +124,8 @@ class StreamSink:
         stride_b, stride_s = self.H * self.n * 4, self.NBUF * self.H * self.n * 4
         ptrs = (C.c_void_p * E)(*(self._row_ptr0 + slots * stride_s + b * stride_b + t * self.n * 4).tolist())
         pred = np.empty(E, np.float64) if self.coeffs is not None else None
-        _lib.check(self.L.mjrl_host_stage_rows_f64x(
-            obs.ctypes.data, E, self.n, ptrs, self.lo.ctypes.data, self.hi.ctypes.data,
-            None if pred is None else self.coeffs.ctypes.data, t.ctypes.data, None if pred is None else pred.ctypes.data,
-            self.flag.ctypes.data), "mjrl_host_stage_rows_f64x")
+        self.S.mjrl_host_stage_rows_f64x(obs, E, self.n, ptrs, self.lo, self.hi,
+                                         None if pred is None else self.coeffs, t, pred, self.flag)
         if pred is not None:
             self.pred_h[slots, b, t] = pred
         # row t arriving means rows < t are complete (their actions and rewards were
@@ -216,14 +214,13 @@ class StreamSink:
             start = torch.from_numpy(np.arange(N, dtype=np.int64) * H - offs[:-1]).to(dev)
             idx = torch.arange(T, dtype=torch.int64, device=dev) + torch.repeat_interleave(
                 start, torch.from_numpy(lengths).to(dev), output_size=T)
-            L = _lib.lib()
+            K = _lib.calls()
             st = _lib.stream_ptr()
             for name, pad, k, dt in pads:
                 dst = _STAGING.device_slot(name, T * k, dt, dev) if reuse else \
                     torch.empty(T * k, dtype=torch.float32 if dt == np.float32 else torch.float64, device=dev)
                 if T:
-                    _lib.check(L.mjrl_gather_rows(_lib.ptr(pad), k * np.dtype(dt).itemsize, _lib.ptr(idx), T,
-                                                  _lib.ptr(dst), st), "mjrl_gather_rows")
+                    K.mjrl_gather_rows(pad, k * np.dtype(dt).itemsize, idx, T, dst, st)
                 out[name] = dst.view(T, k) if k > 1 else dst
         obs, act, rew = out["obs"], out["act"], out["rew"]
         if self.pred_pad is not None:

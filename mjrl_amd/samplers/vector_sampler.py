@@ -17,8 +17,6 @@ as the reference leaves it (the last trajectory's stream).  The mean action is
 the f32 MuNet forward (index-order f32 sums: equal to the CPU forward up to f32
 rounding).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -48,8 +46,7 @@ class BatchedPolicy:
             eng.set_transformations(*self.policy.transformations())
             theta = torch.from_numpy(np.ascontiguousarray(self.policy.get_param_values(), dtype=np.float32))
             theta = eng._pad(theta.to(self.device), "act")
-            _lib.check(eng.lib.mjrl_pack_params(C.byref(eng.shape), _lib.ptr(theta), _lib.ptr(self.packed), 0,
-                                                eng.min_log_std, _lib.stream_ptr()), "mjrl_pack_params")
+            eng.K.mjrl_pack_params(eng.shape, theta, self.packed, 0, eng.min_log_std, _lib.stream_ptr())
         self.log_std_val = np.float64(self.policy.log_std.data.numpy().ravel())
 
     def means(self, observations):
@@ -60,10 +57,7 @@ class BatchedPolicy:
             obs = torch.from_numpy(np.ascontiguousarray(observations, dtype=np.float32)).to(self.device)
             out = torch.empty((N, self.policy.m), dtype=torch.float32, device=self.device)
             ins, isc, osh, osc = eng.transforms
-            p = lambda t: None if t is None else _lib.ptr(t)
-            _lib.check(eng.lib.mjrl_policy_mean(C.byref(eng.shape), _lib.ptr(obs), N, _lib.ptr(self.packed), p(ins),
-                                                p(isc), p(osh), p(osc), _lib.ptr(out), _lib.stream_ptr()),
-                       "mjrl_policy_mean")
+            eng.K.mjrl_policy_mean(eng.shape, obs, N, self.packed, ins, isc, osh, osc, out, _lib.stream_ptr())
             return out.cpu().numpy()
 
 

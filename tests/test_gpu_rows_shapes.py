@@ -126,3 +126,80 @@ def test_fused_path_vs_fp64(n, m, h, T):
     for a, b in zip(offs[:-1], offs[1:]):
         assert nrel(g[a:b], vpg64[a:b]) < 1e-4, (a, b, nrel(g[a:b], vpg64[a:b]))
         assert nrel(fv[a:b], fv64[a:b]) < 1e-4, (a, b, nrel(fv[a:b], fv64[a:b]))
+
+
+def _cg_state(eng, k):
+    """(x, r, p) of the update's CG after k iterations, cloned.  The buffer parity
+    rule lives here: r alternates r / r2 every iteration on every schedule, p
+    alternates p / p2 only on the mjrl_cg_step1 schedule (the others update p in
+    place).  k = 0 is cg_solve's initial state, x = 0 and r = p = g."""
+    v = eng.vec
+    if k == 0:
+        g = v["g"].clone()
+        return torch.zeros_like(g), g, g.clone()
+    r = v["r2"] if k % 2 else v["r"]
+    p = v["p2"] if (k % 2 and _cg_step1(eng)) else v["p"]
+    return v["x"].clone(), r.clone(), p.clone()
+
+
+def _cg_step1(eng):
+    """Whether update() runs this shape's CG on the mjrl_cg_step1 schedule: more
+    64-parameter chunks than the CG state holds p.z partials for."""
+    from mjrl_amd import _lib
+    return (eng.shape.d + 63) // 64 > (_lib.CG_STATE - _lib.CG_PZ_PARTS) // 2
+
+
+@pytest.mark.parametrize("n,m,h,step1", [
+    (130, 3, (256, 256), True),    # wide: d = 100,102 = 1,565 chunks of 64 > 1,536: the mjrl_cg_step1 schedule
+    (39, 28, (256, 256), False),   # door (control): the fused gather + mjrl_cg_step_xr_p schedule
+])
+def test_update_cg_iterations_teacher_forced(n, m, h, step1):
+    """Single CG iterations of update() on the k_rows + k_wgrad shapes, each forced
+    from the update's own state after K iterations: z = F p_K + damping p_K from the
+    standalone eng.fvp (mjrl_cg_init + mjrl_policy_fvp + mjrl_cg_step: other
+    launches than the update's), one step of cg_solve (mjrl/utils/cg_solve.py:9-20)
+    in fp64 on the host, against the state update(cg_iters=K + 1) leaves.  The wide
+    shape has more 64-parameter chunks than the CG state holds p.z partials for, so
+    its iterations run all-reduce + mjrl_cg_step1; the door shape is the control
+    (its schedule is pinned to the reference by the c5 fixtures).  T = 70 rows in
+    two ragged paths: every 16- and 32-row tile is partial.  Bound: 1e-5
+    norm-relative, the bar for a teacher-forced CG iteration."""
+    from mjrl_amd.comm import LocalComm
+    from mjrl_amd.engine import UpdateEngine, DeviceBatch
+    rs = np.random.RandomState(n * 1000 + m)
+    lengths = np.array([33, 37])
+    T = int(lengths.sum())
+    d = h[0] * n + h[0] + h[1] * h[0] + h[1] + m * h[1] + m + m
+    theta = (rs.randn(d) * 0.1).astype(np.float32)
+    theta[-m:] = np.linspace(-1.0, 0.3, m)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    batch = DeviceBatch(t(rs.randn(T, n).astype(np.float32)), t(rs.randn(T, m).astype(np.float32)), t(rs.randn(T)),
+                        t(rs.randn(T)), t(off), t(np.zeros(2, dtype=np.uint8)))
+    eng = UpdateEngine(n, m, h, device="cuda:0", comm=LocalComm())
+    eng.graphs = False
+    assert eng.accumulate_path() == 0 and eng.shape.d == d
+    assert _cg_step1(eng) == step1
+    th = t(theta)
+    damping = 1e-4
+
+    def run(K):
+        res = eng.update(batch, th, algo="npg", cg_iters=K, damping=damping, graph=False)
+        assert res["cg_iters"] == K, res["cg_iters"]   # no early exit: every iteration ran
+        return [a.cpu().numpy().astype(np.float64) for a in _cg_state(eng, K)]
+
+    for K in range(3):
+        x0, r0, p0 = run(K)
+        x1, r1, p1 = run(K + 1)
+        z = eng.fvp(t(p0.astype(np.float32)), damping=damping).cpu().numpy().astype(np.float64)
+        # one iteration of cg_solve.py:9-20 in fp64
+        rdotr = r0.dot(r0)
+        a = rdotr / p0.dot(z)
+        xh = x0 + a * p0
+        rh = r0 - a * z
+        ph = rh + (rh.dot(rh) / rdotr) * p0
+        nx = np.linalg.norm(x0) if K else np.linalg.norm(xh)
+        errs = (np.linalg.norm(x1 - xh) / nx, np.linalg.norm(r1 - rh) / np.linalg.norm(r0),
+                np.linalg.norm(p1 - ph) / np.linalg.norm(p0))
+        print("cg iteration %d (step1=%s): x %.3g r %.3g p %.3g" % (K, step1, *errs))
+        assert max(errs) < 1e-5, (K, errs)
