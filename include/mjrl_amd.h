@@ -461,6 +461,18 @@ int mjrl_trpo_trial(const mjrl_shape* s, const float* x, const float* theta, flo
 int mjrl_policy_mean(const mjrl_shape* s, const float* obs, int64_t N, const float* packed_theta,
                      const float* in_shift, const float* in_scale, const float* out_shift,
                      const float* out_scale, float* mean, void* stream);
+/* mjrl_policy_mean reading the observations where a sampler's environment workers
+ * leave them (samplers/env_workers.py): obs64 [S][n] f64, one row per environment
+ * slot; live[0..E) distinct slot indices, each < S (int32; an index outside [0, S)
+ * is skipped); mean [S][m] f32, of which only the rows live[i] are written.  A row
+ * is rounded to f32 in the kernel ((float)x, round to nearest even) and then goes
+ * through mjrl_policy_mean's arithmetic: row live[i] of mean is bitwise
+ * mjrl_policy_mean of float32(obs64[live[i]]).  All pointers are device pointers.
+ * MJRL_EINVAL for E < 0, S < 0, E > S, E > 0 with obs64 or live null; E == 0 is
+ * MJRL_OK without a launch. */
+int mjrl_policy_mean_slots(const mjrl_shape* s, const double* obs64, const int32_t* live, int64_t E, int64_t S,
+                           const float* packed_theta, const float* in_shift, const float* in_scale,
+                           const float* out_shift, const float* out_scale, float* mean, void* stream);
 
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----

@@ -74,6 +74,10 @@ class BatchREINFORCE:
     sampler = None
     env_factory = None
     num_envs = 64
+    # with the "vector" sampler: worker processes that step the environments
+    # (samplers/env_workers.py; env_factory must then pickle); 0: the default from
+    # MJRL_AMD_SAMPLER_WORKERS, else every environment in this process
+    sampler_workers = 0
     # with the "vector" sampler: stage each trajectory to HBM while sampling goes on
     # (samplers/stream_staging.py; float32 staging, no demonstration rows)
     stream_staging = True
@@ -141,6 +145,12 @@ class BatchREINFORCE:
         if kind not in ("reference", "vector"):
             raise ValueError("sampler must be 'reference' or 'vector', got %r" % kind)
         return kind
+
+    def _sampler_workers(self):
+        k = self.sampler_workers or int(os.environ.get("MJRL_AMD_SAMPLER_WORKERS", "0") or 0)
+        if k < 0:
+            raise ValueError("sampler_workers must be >= 0, got %r" % k)
+        return k
 
     def _pool(self):
         """The GPU worker pool of this agent (mjrl_amd/pool.py) when it runs on
@@ -239,7 +249,8 @@ class BatchREINFORCE:
                 sink = None
             paths = sample_paths_vectorized(N, self.policy, T, env=self.env_factory, env_name=env_name,
                                             pegasus_seed=self.seed, num_envs=self.num_envs,
-                                            device=self.engine().device, sink=sink)
+                                            device=self.engine().device, sink=sink,
+                                            num_workers=self._sampler_workers())
             if sinks:
                 self._stream = sinks[0]
         elif sample_mode == "trajectories":

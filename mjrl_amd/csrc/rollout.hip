@@ -16,19 +16,22 @@ namespace {
 
 constexpr int ACT_ROWS = 4;   // rows (waves) per workgroup
 
-__global__ void __launch_bounds__(64 * ACT_ROWS) k_policy_mean(mjrl_shape s, const float* __restrict__ obs, int64_t N,
-                                                              const float* __restrict__ P,
-                                                              const float* __restrict__ in_shift,
-                                                              const float* __restrict__ in_scale,
-                                                              const float* __restrict__ out_shift,
-                                                              const float* __restrict__ out_scale,
-                                                              float* __restrict__ mean) {
-    extern __shared__ float sm[];
+// The forward of one row by one wave (all 64 * ACT_ROWS threads of the workgroup
+// call it: it holds the barriers).  ObsT: float, or double rounded to float here
+// ((float)x: round to nearest even, numpy's astype(float32)) before anything else,
+// so both entry points run the same f32 arithmetic.  `row` indexes obs [.][n] and
+// mean [.][m]; a wave with live == false computes on zeros and writes nothing.
+template <typename ObsT>
+__device__ __forceinline__ void policy_mean_row(const mjrl_shape& s, const ObsT* __restrict__ obs, int64_t row,
+                                                bool live, const float* __restrict__ P,
+                                                const float* __restrict__ in_shift,
+                                                const float* __restrict__ in_scale,
+                                                const float* __restrict__ out_shift,
+                                                const float* __restrict__ out_scale, float* __restrict__ mean,
+                                                float* sm) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = s.n, m = s.m, np = s.np, h0 = s.h0, h1 = s.h1;
     const Packed pk(h0, h1, np, s.mp);
-    const int64_t row = (int64_t)blockIdx.x * ACT_ROWS + w;
-    const bool live = row < N;
     float* xs = sm + w * (np + h0 + h1);
     float* a0 = xs + np;
     float* a1 = a0 + h0;
@@ -36,7 +39,7 @@ __global__ void __launch_bounds__(64 * ACT_ROWS) k_policy_mean(mjrl_shape s, con
     for (int c = lane; c < np; c += 64) {
         float x = 0.f;
         if (live && c < n) {
-            x = obs[row * n + c];
+            x = (float)obs[row * n + c];
             if (in_shift) x = (x - in_shift[c]) / (in_scale[c] + 1e-8f);
         } else if (c == n) {
             x = 1.f;
@@ -72,6 +75,36 @@ __global__ void __launch_bounds__(64 * ACT_ROWS) k_policy_mean(mjrl_shape s, con
     }
 }
 
+__global__ void __launch_bounds__(64 * ACT_ROWS) k_policy_mean(mjrl_shape s, const float* __restrict__ obs, int64_t N,
+                                                              const float* __restrict__ P,
+                                                              const float* __restrict__ in_shift,
+                                                              const float* __restrict__ in_scale,
+                                                              const float* __restrict__ out_shift,
+                                                              const float* __restrict__ out_scale,
+                                                              float* __restrict__ mean) {
+    extern __shared__ float sm[];
+    const int64_t row = (int64_t)blockIdx.x * ACT_ROWS + (threadIdx.x >> 6);
+    policy_mean_row<float>(s, obs, row, row < N, P, in_shift, in_scale, out_shift, out_scale, mean, sm);
+}
+
+// The same forward for the E slots live[0..E) of an observation board obs64 [S][n]
+// (f64, one row per environment slot): wave i reads row live[i] and writes row
+// live[i] of mean [S][m].  An index outside [0, S) is skipped, never dereferenced.
+__global__ void __launch_bounds__(64 * ACT_ROWS) k_policy_mean_slots(mjrl_shape s, const double* __restrict__ obs64,
+                                                                    const int32_t* __restrict__ live, int64_t E,
+                                                                    int64_t S, const float* __restrict__ P,
+                                                                    const float* __restrict__ in_shift,
+                                                                    const float* __restrict__ in_scale,
+                                                                    const float* __restrict__ out_shift,
+                                                                    const float* __restrict__ out_scale,
+                                                                    float* __restrict__ mean) {
+    extern __shared__ float sm[];
+    const int64_t i = (int64_t)blockIdx.x * ACT_ROWS + (threadIdx.x >> 6);
+    const int64_t slot = i < E ? (int64_t)live[i] : -1;
+    const bool ok = slot >= 0 && slot < S;
+    policy_mean_row<double>(s, obs64, ok ? slot : 0, ok, P, in_shift, in_scale, out_shift, out_scale, mean, sm);
+}
+
 }  // namespace
 
 extern "C" {
@@ -87,6 +120,20 @@ int mjrl_policy_mean(const mjrl_shape* s, const float* obs, int64_t N, const flo
     const int64_t g = (N + ACT_ROWS - 1) / ACT_ROWS;
     hipLaunchKernelGGL(k_policy_mean, dim3((unsigned)g), dim3(64 * ACT_ROWS), lds, (hipStream_t)stream, *s, obs, N,
                        packed_theta, in_shift, in_scale, out_shift, out_scale, mean);
+    return (int)hipGetLastError();
+}
+
+int mjrl_policy_mean_slots(const mjrl_shape* s, const double* obs64, const int32_t* live, int64_t E, int64_t S,
+                           const float* packed_theta, const float* in_shift, const float* in_scale,
+                           const float* out_shift, const float* out_scale, float* mean, void* stream) {
+    if (!s || !packed_theta || !mean || E < 0 || S < 0 || E > S || (E > 0 && (!obs64 || !live))) return MJRL_EINVAL;
+    if ((in_shift == nullptr) != (in_scale == nullptr) || (out_shift == nullptr) != (out_scale == nullptr))
+        return MJRL_EINVAL;
+    if (E == 0) return MJRL_OK;
+    const size_t lds = (size_t)ACT_ROWS * (s->np + s->h0 + s->h1) * sizeof(float);
+    const int64_t g = (E + ACT_ROWS - 1) / ACT_ROWS;
+    hipLaunchKernelGGL(k_policy_mean_slots, dim3((unsigned)g), dim3(64 * ACT_ROWS), lds, (hipStream_t)stream, *s, obs64,
+                       live, E, S, packed_theta, in_shift, in_scale, out_shift, out_scale, mean);
     return (int)hipGetLastError();
 }
 

@@ -15,7 +15,9 @@ sampler wire format (observations, actions, rewards, agent_infos, env_infos,
 terminated).  Paths come back in trajectory order; numpy's global RNG is left
 as the reference leaves it (the last trajectory's stream).  The mean action is
 the f32 MuNet forward (index-order f32 sums: equal to the CPU forward up to f32
-rounding).
+rounding).  With num_workers >= 1 the environments are stepped by worker
+processes (env_workers.py) and the forward reads their observation board
+(mjrl_policy_mean_slots); the trajectories are the same.
 """
 import numpy as np
 import torch
@@ -60,6 +62,41 @@ class BatchedPolicy:
             eng.K.mjrl_policy_mean(eng.shape, obs, N, self.packed, ins, isc, osh, osc, out, _lib.stream_ptr())
             return out.cpu().numpy()
 
+    def means_slots(self, obs_board, live, out=None):
+        """The mean actions of the environment slots `live` (distinct indices < S)
+        of an observation board obs_board [S][n] (f64 numpy; a view of registered
+        host memory is copied by DMA): f32 [S][m] (numpy, `out` when given) whose
+        rows live[i] are bitwise means(float32(obs_board[live])) and whose other
+        rows are not defined.  The board goes to a device buffer with an async
+        copy and the kernel (mjrl_policy_mean_slots) reads that buffer; when this
+        returns the copy out of obs_board has completed."""
+        eng = self.eng
+        S, E = int(obs_board.shape[0]), len(live)
+        if out is None:
+            out = np.empty((S, self.policy.m), np.float32)
+        if E == 0:
+            return out
+        with torch.cuda.device(self.device):
+            b = getattr(self, "_boards", None)
+            if b is None or b[0].shape[0] != S:
+                b = self._boards = (
+                    torch.empty((S, self.policy.n), dtype=torch.float64, device=self.device),
+                    torch.empty((S,), dtype=torch.int32, device=self.device),
+                    torch.empty((S, self.policy.m), dtype=torch.float32, device=self.device),
+                    torch.empty((S,), dtype=torch.int32).pin_memory(),
+                    torch.empty((S, self.policy.m), dtype=torch.float32).pin_memory())
+            d_obs, d_live, d_mean, h_live, h_mean = b
+            h_live[:E] = torch.from_numpy(np.asarray(live, dtype=np.int32))
+            d_obs.copy_(torch.from_numpy(np.ascontiguousarray(obs_board, dtype=np.float64)), non_blocking=True)
+            d_live[:E].copy_(h_live[:E], non_blocking=True)
+            ins, isc, osh, osc = eng.transforms
+            eng.K.mjrl_policy_mean_slots(eng.shape, d_obs, d_live, E, S, self.packed, ins, isc, osh, osc, d_mean,
+                                         _lib.stream_ptr())
+            h_mean.copy_(d_mean, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            out[live] = h_mean.numpy()[live]
+        return out
+
 
 def _seed_env(env, seed):
     try:
@@ -84,7 +121,7 @@ class _Slot:
 
 
 def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_seed=None, num_envs=64,
-                            device=None, sink=None):
+                            device=None, sink=None, num_workers=0, worker_timeout=900.0):
     """N trajectories on min(num_envs, N) lock-stepped environments.
 
     env: an environment factory (called once per slot) or None with env_name
@@ -93,7 +130,30 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
     and horizon >= the trajectories' length) that receives every observation /
     action row as it is produced and stages each trajectory to HBM when it ends
     (sink.batch(paths) afterwards), or a factory sink(N, horizon, slots) that
-    builds one.  The paths returned are the same either way."""
+    builds one.  The paths returned are the same either way.
+
+    num_workers: 0 steps every environment in this process; K >= 1 steps them in
+    min(K, slots) worker processes (samplers/env_workers.py: the policy forward,
+    the trajectory assignment and the sink stay here; the pool is kept for the
+    next call).  env must then be env_name or a picklable factory (a
+    module-level callable or a functools.partial of one).  The paths have the
+    same keys, dtypes and shapes either way; with workers the observations are
+    the f64 [H][n] rows np.asarray(o, float64).ravel() and the rewards f64,
+    which is what num_workers=0 returns for environments whose observations
+    are 1-D f64 arrays and whose rewards are Python floats (other dtypes and
+    shapes are kept as they are by num_workers=0 only).  worker_timeout: the
+    seconds any wait for the workers may take before the pool is torn down."""
+    if num_workers:
+        if env is None and env_name is None:
+            raise ValueError("sample_paths_vectorized needs env (a factory) or env_name")
+        if N <= 0:
+            return []
+        from . import env_workers
+        pool = env_workers.get_env_pool(env if env is not None else env_name, num_workers, min(int(num_envs), int(N)),
+                                        policy.n, policy.m, worker_timeout)
+        bp = BatchedPolicy(policy, device)
+        pool.register_host()
+        return env_workers.sample_paths(pool, N, bp.means_slots, bp.log_std_val, T, pegasus_seed, sink)
     if env is None:
         if env_name is None:
             raise ValueError("sample_paths_vectorized needs env (a factory) or env_name")
