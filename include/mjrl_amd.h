@@ -474,6 +474,33 @@ int mjrl_policy_mean_slots(const mjrl_shape* s, const double* obs64, const int32
                            const float* packed_theta, const float* in_shift, const float* in_scale,
                            const float* out_shift, const float* out_scale, float* mean, void* stream);
 
+/* ---- MLPBaseline value features formed while sampling (streamed staging) ----
+ * The first n columns of mjrl/baselines/mlp_baseline.py:37-56's features,
+ * float32(clip(x, -10, 10) / 10) of the sampler's f64 observation x (no f32 image of
+ * x gives these bits), computed from the observation board mjrl_policy_mean_slots
+ * reads, each row written to its final place:
+ * feat[dest[i]][c] = (float)(clip(obs64[live[i]][c]) / 10.0) for i < E, c < n, with
+ * clip(x) = x < -10 ? -10 : (x > 10 ? 10 : x) (a NaN stays a NaN, -0.0 stays -0.0,
+ * as np.clip), an f64 division and a round-to-nearest-even conversion.  obs64 [S][n]
+ * f64, live [E] int32, dest [E] int64, feat [rows_cap][n] f32, all device pointers.
+ * A live[i] outside [0, S) or a dest[i] outside [0, rows_cap) skips its row: nothing
+ * is written outside feat.  MJRL_EINVAL for a negative size, E > S, n <= 0, or E > 0
+ * with obs64, live, dest or feat null; E == 0 is MJRL_OK without a launch. */
+int mjrl_value_features_slots(const double* obs64, const int32_t* live, const int64_t* dest, int64_t E, int64_t S,
+                              int32_t n, int64_t rows_cap, float* feat, void* stream);
+/* The matrix the value network reads, in one pass: out [T][n + 4] f32,
+ * out[i][0..n) = feat_pad[r][0..n), out[i][n + j] = time_tab[(r % H) * 4 + j], with
+ * r = src_row[i], the row's place ep * H + t in the padded slab feat_pad
+ * [rows_cap][n] (src_row null: r = i, every trajectory ran the horizon H; then
+ * T <= rows_cap).  time_tab [H][4] f32 holds float32((t / 1000) ^ (j + 1)).  A
+ * src_row[i] outside [0, rows_cap) leaves row i of out unwritten.  Rows move as
+ * 16-byte words when n is a multiple of 4 and the three base addresses of 16 (8-byte
+ * words for even n, 4-byte otherwise: the row pitches n and n + 4 floats allow no
+ * wider).  MJRL_EINVAL for a negative size, n <= 0, H <= 0, or T > 0 with feat_pad,
+ * time_tab or out null; T == 0 is MJRL_OK without a launch. */
+int mjrl_value_features_finish(const float* feat_pad, const int64_t* src_row, int64_t T, int32_t n, int64_t rows_cap,
+                               int64_t H, const float* time_tab, float* out, void* stream);
+
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----
  * dst[rows][n] = float(src) (round to nearest, as torch .float()), and when cmin /

@@ -115,6 +115,8 @@ SIGNATURES = {
     "mjrl_trpo_trial": [SP, P, P, F32, P, P, P, P, F64, F64, I32, I32, P, P, P],
     "mjrl_policy_mean": [SP, P, I64, P, P, P, P, P, P, P],
     "mjrl_policy_mean_slots": [SP, P, P, I64, I64, P, P, P, P, P, P, P],
+    "mjrl_value_features_slots": [P, P, P, I64, I64, I32, I64, P, P],
+    "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
     "mjrl_build_flags": [],
     "mjrl_host_stage_f64": [P, I64, I32, P, P, P],
     "mjrl_host_stage_f32": [P, I64, I32, P, P, P],

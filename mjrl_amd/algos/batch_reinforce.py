@@ -79,7 +79,8 @@ class BatchREINFORCE:
     # MJRL_AMD_SAMPLER_WORKERS, else every environment in this process
     sampler_workers = 0
     # with the "vector" sampler: stage each trajectory to HBM while sampling goes on
-    # (samplers/stream_staging.py; float32 staging, no demonstration rows)
+    # (samplers/stream_staging.py; float32 staging, or an MLPBaseline, whose value
+    # features are then formed on the device while sampling; no demonstration rows)
     stream_staging = True
     # dtype the sampled observations / actions are staged to HBM in: float32 (the
     # policy's own input precision, half the PCIe bytes) or float64; None = auto
@@ -238,12 +239,17 @@ class BatchREINFORCE:
                                  "process keeps off the GPUs: use the reference samplers there")
             from ..samplers.vector_sampler import sample_paths_vectorized
             sinks = []
-            if self.stream_staging and self.staging_obs_dtype() == np.float32 and self._demo_paths() is None:
+            # a baseline that predicts from ready features (MLPBaseline) has them formed
+            # on the device from the sampler's f64 values while sampling: the sink then
+            # stages f32 rows for it too (unless the caller asked for a staging dtype)
+            feats = self.staging_dtype is None and hasattr(self.baseline, "predict_features_device")
+            if self.stream_staging and (self.staging_obs_dtype() == np.float32 or feats) \
+                    and self._demo_paths() is None:
                 from ..samplers.stream_staging import StreamSink
 
                 def sink(n_paths, horizon, nslots):
                     sinks.append(StreamSink(self.policy.n, self.policy.m, horizon, n_paths, self.engine().device,
-                                            baseline=self.baseline, nslots=nslots))
+                                            baseline=self.baseline, nslots=nslots, value_features=feats))
                     return sinks[-1]
             else:
                 sink = None
@@ -343,7 +349,8 @@ class BatchREINFORCE:
         """baseline.fit(paths) (batch_reinforce.py:93-101).  A LinearBaseline, and a
         QuadraticBaseline of up to QUADRATIC_DEVICE_MAX_N observation columns, is
         fitted on the device from the batch still in HBM (its Gram products are
-        the T x k work); other baselines fit on the host.
+        the T x k work); an MLPBaseline from the feature matrix
+        a streamed batch carries (batch.value_feat); other baselines fit on the host.
         Sharded (world > 1), every rank fits on the union of all ranks' paths:
         the LinearBaseline Gram is all-reduced on device, a baseline with ridge
         normal equations (_features / _reg_coeff: Quadratic) all-reduces its
@@ -362,6 +369,14 @@ class BatchREINFORCE:
             fit = self.engine().fit_linear_baseline if kind == "LinearBaseline" else \
                 self.engine().fit_quadratic_baseline
             return fit(batch, self.baseline, return_errors=return_errors, obs_lo=batch.obs_lo(paths))
+        feat = getattr(batch, "value_feat", None)
+        if feat is not None and comm.world_size == 1 and hasattr(self.baseline, "fit_features_device") \
+                and feat.shape[0] == batch.T == sum(len(p["rewards"]) for p in paths):
+            # MLPBaseline on a streamed batch: its feature matrix and the returns of the
+            # GAE scan are still in HBM (what fit(paths) would rebuild on the host and
+            # upload, bit for bit)
+            return self.baseline.fit_features_device(feat, self.engine().ws["ret"][:batch.T],
+                                                     return_errors=return_errors)
         if comm.world_size > 1:
             return _fit_sharded(self.baseline, paths, comm, return_errors)
         return self.baseline.fit(paths, return_errors=return_errors) if return_errors else self.baseline.fit(paths)

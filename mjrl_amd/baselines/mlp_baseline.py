@@ -332,10 +332,32 @@ class MLPBaseline:
         o = (obs[:T].to(torch.float64).clamp(-10.0, 10.0) / 10.0).to(torch.float32)
         # the time features depend on the row's index in its path only: one f32
         # table from numpy's own al ** (j + 1) (torch's pow takes other roundings)
-        al = np.arange(int(lengths.max()) if len(lengths) else 0) / 1000.0
-        tab = torch.from_numpy(np.stack([al ** (j + 1) for j in range(4)], 1).astype(np.float32)).to(dev)
+        tab = self.time_table(int(lengths.max()) if len(lengths) else 0, dev)
         start = torch.repeat_interleave(path_off[:-1], torch.from_numpy(lengths).to(dev))
         return torch.cat([o, tab[torch.arange(T, device=dev, dtype=torch.int64) - start]], 1)
+
+    @staticmethod
+    def time_table(H, dev):
+        """The four time features of path indices 0 .. H - 1, f32 [H][4] on dev:
+        numpy's own al ** (j + 1) (torch's pow takes other roundings)."""
+        al = np.arange(int(H)) / 1000.0
+        return torch.from_numpy(np.stack([al ** (j + 1) for j in range(4)], 1).astype(np.float32)).to(dev)
+
+    def predict_features_device(self, feat):
+        """predict_device's forward on a ready feature matrix (device f32
+        [T][n + 4], features_device's bits: the streamed staging forms it while
+        sampling, samplers/stream_staging.py) -> f64 device [T]."""
+        st = self._predict_state()
+        with torch.no_grad():
+            return st["model"](feat).to(torch.float64).reshape(-1)
+
+    def fit_features_device(self, feat, returns_dev, return_errors=False):
+        """fit(paths) from the batch still in HBM: feat as predict_features_device
+        takes it, returns_dev the paths' returns (device f64 [T]); the same
+        minibatch draws from numpy's global RNG, the same steps."""
+        st = self._to_device()
+        Y = returns_dev.to(torch.float32).reshape(-1, 1)
+        return self._fit_device(st, feat, Y, return_errors, comm=None)
 
     def predict(self, path):
         """mlp_baseline.py:107-115: one forward of the f32 features (on the GPU

@@ -21,6 +21,15 @@ sampling loop of samplers/vector_sampler.py:
     stepping (so the last lock step leaves at most FLUSH_ROWS rows a slot to
     copy);
   - rewards and the predictions travel the same way (8 bytes a row each);
+  - with value_features=True (an MLPBaseline, whose features float32(clip(x) / 10)
+    need the f64 x): every lock step, mjrl_value_features_slots forms the live
+    rows' features on the device from the step's f64 observations, the board the
+    batched policy forward already uploaded when the environments run in worker
+    processes (attach_board), the step's rows uploaded from here otherwise, and
+    writes each row at its position (ep * H + t) of a padded f32 slab; batch()
+    then builds the [T][n + 4] matrix the value network reads in one pass
+    (mjrl_value_features_finish), runs the forward on it and keeps it on the
+    batch for the fit (batch.value_feat);
   - after sampling, batch() compacts the padded slabs into the contiguous
     layout with one device gather per slot (mjrl_gather_rows; none when every
     trajectory ran the full horizon: the padded slabs are then the batch) and
@@ -42,6 +51,7 @@ from ..engine import DeviceBatch, _STAGING, _linear_coeffs
 
 
 _SLABS = {}
+_VF_BUFS = {}   # the value-feature step buffers of one (slots, n, device) at a time
 
 
 class StreamSink:
@@ -50,15 +60,21 @@ class StreamSink:
     n, m: observation / action widths; horizon: the longest trajectory; N: the
     number of trajectories; baseline: the agent's value baseline (a
     LinearBaseline's coefficients are used for the predictions, as fixed while
-    the batch is sampled); nslots: the sampler's environment slots."""
+    the batch is sampled); nslots: the sampler's environment slots;
+    value_features: form the baseline's observation features on the device while
+    sampling (a baseline with predict_features_device: MLPBaseline)."""
 
     NBUF = 2   # slabs per environment slot: a slot starts its next trajectory while the last one's copy runs
     FLUSH_ROWS = 256   # a live trajectory's completed rows leave for HBM in runs of this many
 
-    def __init__(self, n, m, horizon, N, device, baseline=None, nslots=64):
+    def __init__(self, n, m, horizon, N, device, baseline=None, nslots=64, value_features=False):
         self.n, self.m, self.H, self.N = int(n), int(m), int(horizon), int(N)
         self.device = torch.device(device)
         self.baseline = baseline
+        self.value_features = bool(value_features)
+        if self.value_features and not hasattr(baseline, "predict_features_device"):
+            raise ValueError("StreamSink(value_features=True) needs a baseline with predict_features_device "
+                             "(MLPBaseline), got %r" % (baseline,))
         c = _linear_coeffs(baseline, self.n)
         self.linear = c is not False
         self.coeffs = None if c is False or c is None else np.ascontiguousarray(c, dtype=np.float64)
@@ -96,7 +112,87 @@ class StreamSink:
             self.cs = _STAGING._copy_stream(self.device)
             # the padded slabs may still be read by work queued on the current stream
             self.cs.wait_stream(torch.cuda.current_stream(self.device))
+            if self.value_features:
+                self._init_value_features(S)
         self.done = False
+
+    # ---- value features (MLPBaseline) -------------------------------------------
+    VF_RING = 2   # pinned per-step index (and row) buffers in rotation
+
+    def _init_value_features(self, S):
+        """feat_pad [N H][n] f32 in HBM: row ep H + t is float32(clip(x) / 10) of
+        the f64 observation, written by mjrl_value_features_slots in the lock step
+        that produced it.  Per step the kernel needs dest / live (and, without
+        environment workers, the f64 rows themselves): small pinned buffers in
+        rotation, each with the event of its last use."""
+        n, dev = self.n, self.device
+        self.feat_pad = _STAGING.device_slot("stream_vfeat", self.N * self.H * n, np.float32, dev).view(
+            self.N * self.H, n)
+        key = (S, n, dev)
+        ent = _VF_BUFS.get(key)
+        if ent is None:
+            _VF_BUFS.clear()
+            R = self.VF_RING
+            # idx[r][0] = dest (int64 [S]), idx[r][1] viewed as int32: live [S]
+            ent = _VF_BUFS[key] = dict(h_idx=torch.zeros((R, 2, S), dtype=torch.int64).pin_memory(),
+                                       d_idx=torch.zeros((2, S), dtype=torch.int64, device=dev),
+                                       h_rows=None, d_rows=None, ev=[None] * R, turn=0)
+        self._vf = ent
+        self._board = None
+        self._vf_ev = None
+
+    def attach_board(self, board):
+        """board: the device f64 [S][n] observation board the sampler's policy
+        forward uploads every lock step on the current stream
+        (BatchedPolicy.obs_board): rows() then reads this step's rows there
+        instead of uploading them a second time.  Ignored without value_features."""
+        if not self.value_features:
+            return
+        if board.dtype != torch.float64 or board.dim() != 2 or board.shape[1] != self.n or \
+                board.shape[0] < len(self.buf) or board.device != self.feat_pad.device or not board.is_contiguous():
+            raise ValueError("StreamSink.attach_board: need a contiguous f64 [>= %d][%d] board on %s"
+                             % (len(self.buf), self.n, self.device))
+        self._board = board
+
+    def _feature_rows(self, slots, obs, t):
+        """mjrl_value_features_slots for this lock step's rows, on the current
+        stream: the stream the board upload of this step ran on, so the next
+        step's upload (queued behind it) cannot overtake the kernel."""
+        vf, E, S = self._vf, len(slots), len(self.buf)
+        r = vf["turn"]
+        vf["turn"] = (r + 1) % self.VF_RING
+        # The pinned buffers of turn r were last read by the copies of VF_RING steps
+        # ago: the event recorded behind that step's copies and kernel is waited for
+        # before they are rewritten, which is what makes the reuse safe.  (The policy
+        # forward of every step in between ends in a synchronise of this stream,
+        # BatchedPolicy.means / means_slots, so the wait returns at once.)
+        if vf["ev"][r] is not None:
+            vf["ev"][r].synchronize()
+        h_idx, d_idx = vf["h_idx"][r], vf["d_idx"]
+        h = h_idx.numpy()
+        h[0, :E] = self.ep[slots] * self.H + t
+        live = h[1].view(np.int32)
+        with torch.cuda.device(self.device):
+            if self._board is not None:
+                live[:E] = slots
+                src, nsrc = self._board, int(self._board.shape[0])
+            else:
+                # no environment workers: this step's f64 rows [E][n] go up from here
+                if vf["h_rows"] is None:
+                    vf["h_rows"] = torch.zeros((self.VF_RING, S, self.n), dtype=torch.float64).pin_memory()
+                    vf["d_rows"] = torch.zeros((S, self.n), dtype=torch.float64, device=self.device)
+                vf["h_rows"][r].numpy()[:E] = obs
+                vf["d_rows"][:E].copy_(vf["h_rows"][r, :E], non_blocking=True)
+                live[:E] = np.arange(E, dtype=np.int32)
+                src, nsrc = vf["d_rows"], S
+            d_idx.copy_(h_idx, non_blocking=True)
+            _lib.calls().mjrl_value_features_slots(src, d_idx[1], d_idx[0], E, nsrc, self.n, self.N * self.H,
+                                                   self.feat_pad, _lib.stream_ptr())
+            ev = vf["ev"][r]
+            if ev is None:
+                ev = vf["ev"][r] = torch.cuda.Event()
+            ev.record()
+        self._vf_ev = ev
 
     # ---- sampler side -------------------------------------------------------
     def begin(self, slot, ep):
@@ -128,6 +224,8 @@ class StreamSink:
                                          None if pred is None else self.coeffs, t, pred, self.flag)
         if pred is not None:
             self.pred_h[slots, b, t] = pred
+        if self.value_features:
+            self._feature_rows(slots, obs, t)
         # row t arriving means rows < t are complete (their actions and rewards were
         # recorded in the previous step): send full runs of them
         due = np.nonzero(t - self.copied[slots] >= self.FLUSH_ROWS)[0]
@@ -204,6 +302,7 @@ class StreamSink:
                 ("rew", self.rew_pad, 1, np.float64)] + \
             ([("base", self.pred_pad, 1, np.float64)] if self.pred_pad is not None else [])
         out = {}
+        idx = None
         if T == N * H:
             # every trajectory ran the full horizon: the padded slabs are the batch
             for name, pad, k, _ in pads:
@@ -223,8 +322,23 @@ class StreamSink:
                     K.mjrl_gather_rows(pad, k * np.dtype(dt).itemsize, idx, T, dst, st)
                 out[name] = dst.view(T, k) if k > 1 else dst
         obs, act, rew = out["obs"], out["act"], out["rew"]
+        value_feat = None
         if self.pred_pad is not None:
             base = out["base"]
+        elif self.value_features:
+            # MLPBaseline: the matrix its network reads, [T][n + 4], in one pass over
+            # the feature slab (compaction by the gather's own index, the time columns
+            # from the baseline's table), then one forward
+            k = self.n + 4
+            value_feat = (_STAGING.device_slot("value_feat", T * k, np.float32, dev) if reuse else
+                          torch.empty(T * k, dtype=torch.float32, device=dev)).view(T, k)
+            if self._vf_ev is not None:
+                cur.wait_event(self._vf_ev)   # the last lock step's features
+            if T:
+                _lib.calls().mjrl_value_features_finish(self.feat_pad, idx, T, self.n, N * H, H,
+                                                        self.baseline.time_table(H, dev), value_feat,
+                                                        _lib.stream_ptr())
+            base = self.baseline.predict_features_device(value_feat)
         elif not self.linear and self.baseline is not None:
             # another baseline: its own predict per path, as DeviceBatch.from_paths
             # (process_samples.py:23)
@@ -236,5 +350,7 @@ class StreamSink:
         b = DeviceBatch(obs, act, rew, base, off, term, obs_range=orange)
         b.lengths = lengths
         b.obs_inexact = bool(self.flag[0])
+        if value_feat is not None:
+            b.value_feat = value_feat   # kept for the baseline fit (MLPBaseline.fit_features_device)
         self.done = True
         return b

@@ -62,6 +62,27 @@ class BatchedPolicy:
             eng.K.mjrl_policy_mean(eng.shape, obs, N, self.packed, ins, isc, osh, osc, out, _lib.stream_ptr())
             return out.cpu().numpy()
 
+    def _board_set(self, S):
+        """The device and pinned buffers of means_slots for S slots, kept across steps."""
+        b = getattr(self, "_boards", None)
+        if b is None or b[0].shape[0] != S:
+            with torch.cuda.device(self.device):
+                b = self._boards = (
+                    torch.empty((S, self.policy.n), dtype=torch.float64, device=self.device),
+                    torch.empty((S,), dtype=torch.int32, device=self.device),
+                    torch.empty((S, self.policy.m), dtype=torch.float32, device=self.device),
+                    torch.empty((S,), dtype=torch.int32).pin_memory(),
+                    torch.empty((S, self.policy.m), dtype=torch.float32).pin_memory())
+        return b
+
+    def obs_board(self, S):
+        """The device copy of the observation board (f64 [S][n]) that means_slots
+        fills every lock step on the current stream: after a means_slots call it
+        holds that step's observations until the next call's copy, which is
+        ordered behind whatever was queued on that stream in between (a
+        StreamSink forms the value features from it: attach_board)."""
+        return self._board_set(int(S))[0]
+
     def means_slots(self, obs_board, live, out=None):
         """The mean actions of the environment slots `live` (distinct indices < S)
         of an observation board obs_board [S][n] (f64 numpy; a view of registered
@@ -77,15 +98,7 @@ class BatchedPolicy:
         if E == 0:
             return out
         with torch.cuda.device(self.device):
-            b = getattr(self, "_boards", None)
-            if b is None or b[0].shape[0] != S:
-                b = self._boards = (
-                    torch.empty((S, self.policy.n), dtype=torch.float64, device=self.device),
-                    torch.empty((S,), dtype=torch.int32, device=self.device),
-                    torch.empty((S, self.policy.m), dtype=torch.float32, device=self.device),
-                    torch.empty((S,), dtype=torch.int32).pin_memory(),
-                    torch.empty((S, self.policy.m), dtype=torch.float32).pin_memory())
-            d_obs, d_live, d_mean, h_live, h_mean = b
+            d_obs, d_live, d_mean, h_live, h_mean = self._board_set(S)
             h_live[:E] = torch.from_numpy(np.asarray(live, dtype=np.int32))
             d_obs.copy_(torch.from_numpy(np.ascontiguousarray(obs_board, dtype=np.float64)), non_blocking=True)
             d_live[:E].copy_(h_live[:E], non_blocking=True)
@@ -120,6 +133,24 @@ class _Slot:
     __slots__ = ("env", "ep", "rs", "o", "t", "obs", "act", "rew", "ainfo", "einfo", "idx")
 
 
+def _with_board(sink, bp, S):
+    """The sink (or sink factory) of a worker-stepped sampling call, given the
+    device observation board of bp.means_slots when it can use one (a sink with
+    an attach_board method); any other sink is passed on as it is."""
+    if sink is None:
+        return None
+    if callable(sink):
+        def make(*args):
+            s = sink(*args)
+            if hasattr(s, "attach_board"):
+                s.attach_board(bp.obs_board(S))
+            return s
+        return make
+    if hasattr(sink, "attach_board"):
+        sink.attach_board(bp.obs_board(S))
+    return sink
+
+
 def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_seed=None, num_envs=64,
                             device=None, sink=None, num_workers=0, worker_timeout=900.0):
     """N trajectories on min(num_envs, N) lock-stepped environments.
@@ -130,7 +161,9 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
     and horizon >= the trajectories' length) that receives every observation /
     action row as it is produced and stages each trajectory to HBM when it ends
     (sink.batch(paths) afterwards), or a factory sink(N, horizon, slots) that
-    builds one.  The paths returned are the same either way.
+    builds one.  The paths returned are the same either way.  With workers, a sink
+    that has an attach_board method is handed the device observation board of the
+    policy forward (BatchedPolicy.obs_board).
 
     num_workers: 0 steps every environment in this process; K >= 1 steps them in
     min(K, slots) worker processes (samplers/env_workers.py: the policy forward,
@@ -153,7 +186,8 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
                                         policy.n, policy.m, worker_timeout)
         bp = BatchedPolicy(policy, device)
         pool.register_host()
-        return env_workers.sample_paths(pool, N, bp.means_slots, bp.log_std_val, T, pegasus_seed, sink)
+        return env_workers.sample_paths(pool, N, bp.means_slots, bp.log_std_val, T, pegasus_seed,
+                                        _with_board(sink, bp, pool.S))
     if env is None:
         if env_name is None:
             raise ValueError("sample_paths_vectorized needs env (a factory) or env_name")

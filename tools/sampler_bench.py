@@ -8,7 +8,10 @@ through the workers (StreamSink.batch -> update -> readback).
 
     python tools/sampler_bench.py [--workers 15] [--envs 64 256] [--delays 0 50 100]
                                   [--horizon 100] [--rounds 2] [--post-paths 256 --post-horizon 1000]
+                                  [--post-only] [--baseline mlp [--alternations 3]]
 
+--baseline mlp times an MLPBaseline agent instead (sampling, the post-sampling
+critical path and the baseline fit), the streamed staging off and on in turn.
 Prints one JSON line per configuration and a summary line with the ratios.  The
 baseline of every ratio is num_workers=0 in the same run.  Needs a GPU (the
 policy forward).  Imported by the workers too (the environment class lives
@@ -82,6 +85,10 @@ def main():
     ap.add_argument("--post-paths", type=int, default=256, help="0: skip the post-sampling measurement")
     ap.add_argument("--post-horizon", type=int, default=1000)
     ap.add_argument("--post-delay", type=float, default=50)
+    ap.add_argument("--post-only", action="store_true", help="skip the worker / in-process sampling table")
+    ap.add_argument("--baseline", choices=("linear", "mlp"), default="linear",
+                    help="mlp: an NPG agent with an MLPBaseline, the streamed staging on against off")
+    ap.add_argument("--alternations", type=int, default=3, help="--baseline mlp: off / on pairs timed")
     args = ap.parse_args()
     import torch
     import sampler_bench   # the workers unpickle the environment factory by this module's name
@@ -93,7 +100,7 @@ def main():
     policy = MLP(EnvSpec(N_OBS, N_ACT, args.horizon, 1), hidden_sizes=(64, 64), seed=0, init_log_std=-1.0)
     H = args.horizon
     rows = {}
-    for S in args.envs:
+    for S in ([] if args.post_only else args.envs):
         N = S * args.rounds
         for d in args.delays:
             env = functools.partial(sampler_bench.DelayEnv, d, H)
@@ -109,13 +116,90 @@ def main():
                 rows[(S, d, W)] = r
                 print(json.dumps(r), flush=True)
         env_workers.close_env_pools()
-    summary = [dict(num_envs=S, step_us=d, workers_over_in_process=round(
-        rows[(S, d, args.workers)]["rows_per_s"] / rows[(S, d, 0)]["rows_per_s"], 2))
-        for S in args.envs for d in args.delays]
-    print(json.dumps(dict(summary=summary, num_workers=args.workers)), flush=True)
+    if not args.post_only:
+        summary = [dict(num_envs=S, step_us=d, workers_over_in_process=round(
+            rows[(S, d, args.workers)]["rows_per_s"] / rows[(S, d, 0)]["rows_per_s"], 2))
+            for S in args.envs for d in args.delays]
+        print(json.dumps(dict(summary=summary, num_workers=args.workers)), flush=True)
     if args.post_paths:
-        _post_sampling(args, policy.hidden_sizes, sampler_bench)
+        (_post_sampling_mlp if args.baseline == "mlp" else _post_sampling)(args, policy.hidden_sizes, sampler_bench)
     env_workers.close_env_pools()
+
+
+def _post_sampling_mlp(args, hidden, sampler_bench):
+    """An NPG agent with an MLPBaseline, train_step's own stages timed apart, the
+    streamed staging off (the finished f64 paths staged after sampling, the
+    features rebuilt on the host for the fit) and on (StreamSink with
+    value_features), alternating: rows/s while sampling, the post-sampling critical
+    path (staging or StreamSink.batch -> value forward -> update -> readback) and
+    _fit_baseline; and the sampling alone with the sink fed but no features formed
+    (what the feature kernel itself adds to a lock step).  Both routes compute the
+    same numbers (tests/test_gpu_value_features.py); every pair starts from the
+    same agent state."""
+    import copy
+    import torch
+    from mjrl_amd.algos.npg_cg import NPG
+    from mjrl_amd.baselines.mlp_baseline import MLPBaseline
+    from mjrl_amd.policies.gaussian_mlp import MLP
+    from mjrl_amd.samplers.stream_staging import StreamSink
+    from mjrl_amd.samplers.vector_sampler import sample_paths_vectorized
+    from mjrl_amd.utils.gym_env import EnvSpec
+    N, H, S = args.post_paths, args.post_horizon, args.envs[0]
+    spec = EnvSpec(N_OBS, N_ACT, H, 1)
+
+    class Env:
+        env_id = "delay-v0"
+    agent = NPG(Env(), MLP(spec, hidden_sizes=hidden, seed=0, init_log_std=-1.0), MLPBaseline(spec),
+                normalized_step_size=0.01, seed=1, save_logs=False, device="cuda:0")
+    env = functools.partial(sampler_bench.DelayEnv, args.post_delay, H)
+    dev = agent.engine().device
+    theta0 = agent.policy.get_param_values().copy()
+    base0 = copy.deepcopy((agent.baseline.model.state_dict(), agent.baseline.optimizer.state_dict()))
+
+    def one(stream, features=True):
+        agent.policy.set_param_values(theta0.copy(), set_new=True, set_old=True)
+        agent.baseline.model.load_state_dict(base0[0])
+        agent.baseline.optimizer.load_state_dict(copy.deepcopy(base0[1]))
+        sinks = []
+
+        def make(n_paths, horizon, nslots):
+            sinks.append(StreamSink(N_OBS, N_ACT, horizon, n_paths, dev, baseline=agent.baseline, nslots=nslots,
+                                    value_features=features))
+            return sinks[-1]
+        np.random.seed(3)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        paths = sample_paths_vectorized(N, agent.policy, 1e6, env=env, pegasus_seed=1, num_envs=S, device=dev,
+                                        sink=make if stream else None, num_workers=args.workers)
+        t1 = time.perf_counter()
+        if not features:   # the sink's own feed without the feature kernel: sampling only
+            torch.cuda.synchronize()
+            return dict(stream="no_features", rows_per_s=round(N * H / (t1 - t0), 1), sampling_s=round(t1 - t0, 4))
+        if stream:
+            agent._stream = sinks[0]
+        agent.train_from_samples(paths, 0.995, 0.97)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        agent._fit_baseline(paths)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        return dict(stream=stream, rows_per_s=round(N * H / (t1 - t0), 1), sampling_s=round(t1 - t0, 4),
+                    post_sampling_ms=round((t2 - t1) * 1e3, 2), fit_baseline_ms=round((t3 - t2) * 1e3, 2))
+    for stream in (False, True):   # warm-up: the pool, first launches, the slabs, the captured fit step
+        one(stream)
+    runs = []
+    for _ in range(args.alternations):
+        for stream in (False, True):
+            runs.append(one(stream))
+            print(json.dumps(runs[-1]), flush=True)
+        print(json.dumps(one(True, features=False)), flush=True)
+    out = dict(timesteps=N * H, num_envs=S, num_workers=args.workers, step_us=args.post_delay)
+    for stream in (False, True):
+        mine = [r for r in runs if r["stream"] == stream]
+        for k in ("rows_per_s", "post_sampling_ms", "fit_baseline_ms"):
+            v = [r[k] for r in mine]
+            out["%s_%s" % (k, "on" if stream else "off")] = dict(median=float(np.median(v)), min=min(v), max=max(v))
+    print(json.dumps(out), flush=True)
 
 
 def _post_sampling(args, hidden, sampler_bench):
