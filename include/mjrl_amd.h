@@ -501,6 +501,45 @@ int mjrl_value_features_slots(const double* obs64, const int32_t* live, const in
 int mjrl_value_features_finish(const float* feat_pad, const int64_t* src_row, int64_t T, int32_t n, int64_t rows_cap,
                                int64_t H, const float* time_tab, float* out, void* stream);
 
+/* ---- MLPBaseline.fit's minibatch Adam steps (mjrl/baselines/mlp_baseline.py:83-96) ----
+ * The value network Linear(n + 4, 128) - ReLU - Linear(128, 128) - ReLU -
+ * Linear(128, 1) and its Adam state, device pointers in torch's parameter order
+ * W0 [128][n + 4], b0 [128], W1 [128][128], b1 [128], W2 [1][128], b2 [1]. */
+typedef struct mjrl_value_net {
+    float* p[6];              /* the parameters */
+    float* exp_avg[6];        /* Adam's first moments, the parameters' shapes */
+    float* exp_avg_sq[6];     /* Adam's second moments */
+} mjrl_value_net;
+/* torch.optim.Adam's hyper-parameters and the number of steps already taken. */
+typedef struct mjrl_adam {
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step0;            /* Adam steps already taken */
+} mjrl_adam;
+/* floats of scratch for one net: a0 (twice: even and odd steps), g0, g1 [64][128] each
+ * and the last step's loss (the same for every n and every bs in 1..64).  MJRL_EINVAL for n <= 0, bs outside
+ * 1..64 or a null result. */
+int mjrl_value_mlp_scratch(int32_t n, int32_t bs, int64_t* floats);
+/* nmb minibatch Adam steps of mlp_baseline.py:83-96, enqueued on `stream`:
+ * step k trains on rows perm[k*bs .. k*bs+bs) of X [T][n+4] f32, Y [T] f32 (perm:
+ * device int64, at least nmb*bs entries; an entry outside [0, T) masks its row: it
+ * adds nothing to the gradient, which still divides by bs, and nothing of X / Y is
+ * read for it).  The loss is the MSE of the minibatch; Adam is torch's single-tensor
+ * formula (weight decay added to the gradient), step k with bias corrections
+ * 1 - beta^(step0 + k + 1) formed on the host in fp64.
+ * net: the parameters and moments, updated in place.  hp: see mjrl_adam.
+ * scratch: mjrl_value_mlp_scratch floats.
+ * grad_out: null or [nmb][d], step k's minibatch gradient before weight decay,
+ * in torch parameter order (d = 128 (n+4) + 128 + 128*128 + 128 + 128 + 1).
+ * loss_out: null or [nmb] MSE.
+ * Two launches per step (plus one), exact-f32 MFMA, every sum in one fixed order, no
+ * atomics: the same state and arguments give the same bits.  Never allocates, never
+ * synchronises.  MJRL_EINVAL before any launch for bs outside 1..64, n <= 0 or above 2^24, a negative
+ * T, nmb or step0, and, when nmb > 0, a null X, Y, perm, net, hp, scratch or a null
+ * pointer inside net; nmb == 0 is MJRL_OK without a launch. */
+int mjrl_value_mlp_epoch(const float* X, const float* Y, int64_t T, int32_t n, const int64_t* perm, int64_t nmb,
+                         int32_t bs, const mjrl_value_net* net, const mjrl_adam* hp, float* scratch, float* grad_out,
+                         float* loss_out, void* stream);
+
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----
  * dst[rows][n] = float(src) (round to nearest, as torch .float()), and when cmin /

@@ -46,6 +46,17 @@ class Scratch(C.Structure):
     _fields_ = [("wpart", C.c_void_p), ("rpart", C.c_void_p), ("slices", C.c_int32)]
 
 
+class ValueNet(C.Structure):
+    """mjrl_value_net: the value network's parameters and Adam moments, torch order."""
+    _fields_ = [("p", C.c_void_p * 6), ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6)]
+
+
+class Adam(C.Structure):
+    """mjrl_adam"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("step0", C.c_int64)]
+
+
 P = C.c_void_p
 I32 = C.c_int32
 I64 = C.c_int64
@@ -117,6 +128,8 @@ SIGNATURES = {
     "mjrl_policy_mean_slots": [SP, P, P, I64, I64, P, P, P, P, P, P, P],
     "mjrl_value_features_slots": [P, P, P, I64, I64, I32, I64, P, P],
     "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
+    "mjrl_value_mlp_scratch": [I32, I32, C.POINTER(I64)],
+    "mjrl_value_mlp_epoch": [P, P, I64, I32, P, I64, I32, C.POINTER(ValueNet), C.POINTER(Adam), P, P, P, P],
     "mjrl_build_flags": [],
     "mjrl_host_stage_f64": [P, I64, I32, P, P, P],
     "mjrl_host_stage_f32": [P, I64, I32, P, P, P],

@@ -22,12 +22,25 @@ fit and back after it.  Sharded (fit_sharded, one process per GPU): rank 0's
 permutation is broadcast, every rank computes the minibatch gradient over its
 own rows of each minibatch, the gradients are all-reduced (a sum: the MSE is a
 mean over the global minibatch), and every rank takes the same Adam step.
+
+fit_backend = "hip" (opt-in, per instance or on the class) replaces the graph
+replays of fit / fit_features_device by the hand-written kernels of
+csrc/value_fit.hip: one mjrl_value_mlp_epoch call per epoch on the device
+model's own parameters and the device optimizer's moments, the same permutation
+buffer, batch_size <= 64.  The sharded fit stays on torch
+whatever the attribute says.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from .._capture import capture
+
+FIT_BACKENDS = ("torch", "hip")
+HIP_MAX_BATCH = 64   # rows of a minibatch the fused kernels hold (csrc/value_fit.hip)
 
 
 def _features_np(paths, n):
@@ -50,6 +63,10 @@ def _features_np(paths, n):
 
 
 class MLPBaseline:
+    # "torch": a captured graph of torch ops per minibatch step; "hip": the fused
+    # kernels of csrc/value_fit.hip (fit / fit_features_device only)
+    fit_backend = "torch"
+
     def __init__(self, env_spec, obs_dim=None, learn_rate=1e-3, reg_coef=0.0, batch_size=64, epochs=1,
                  use_gpu=False, device=None):
         self.n = obs_dim if obs_dim is not None else env_spec.observation_dim
@@ -224,7 +241,16 @@ class MLPBaseline:
         X, Y = self._device_data(paths)
         return self._fit_device(st, X, Y, return_errors, comm=comm)
 
+    def _check_backend(self):
+        if self.fit_backend not in FIT_BACKENDS:
+            raise ValueError("MLPBaseline.fit_backend must be one of %s, not %r" % (FIT_BACKENDS, self.fit_backend))
+        if self.fit_backend == "hip" and not 1 <= self.batch_size <= HIP_MAX_BATCH:
+            raise ValueError('MLPBaseline.fit_backend = "hip" takes batch_size 1..%d, not %d'
+                             % (HIP_MAX_BATCH, self.batch_size))
+
     def _fit_device(self, st, X, Y, return_errors, comm):
+        if comm is None:
+            self._check_backend()
         N_local = X.shape[0]
         dev = st["device"]
         if comm is not None and comm.world_size > 1:
@@ -249,7 +275,8 @@ class MLPBaseline:
                 self._epoch_sharded(st, X, Y, perm.to(dev), lo, N_local, comm)
             else:
                 rand_idx = torch.from_numpy(np.random.permutation(N)).to(dev)
-                self._epoch(st, X, Y, rand_idx)
+                # fit_sharded stays on torch, on one rank too
+                self._epoch(st, X, Y, rand_idx, backend="torch" if comm is not None else None)
         if return_errors:
             e, y2 = self._sq_err(st, X, Y)
             error_after = self._ratio(e, y2, comm, dev)
@@ -265,11 +292,16 @@ class MLPBaseline:
             e, y2 = t[0], t[1]
         return float(e.item() / (y2.item() + 1e-8))
 
-    def _epoch(self, st, X, Y, rand_idx):
+    def _epoch(self, st, X, Y, rand_idx, backend=None):
         bs = self.batch_size
         nmb = int(X.shape[0] / bs) - 1
         if nmb <= 0:
             return
+        if backend is None:
+            self._check_backend()
+            backend = self.fit_backend
+        if backend == "hip":
+            return self._epoch_hip(st, X, Y, rand_idx, nmb)
         try:
             st = self._step_graph(st, X, Y)
         except Exception:   # no graph capture available: eager steps, same math
@@ -285,6 +317,41 @@ class MLPBaseline:
                 loss = self.loss_function(model(X[sel]), Y[sel])
                 loss.backward()
                 opt.step()
+
+    def _epoch_hip(self, st, X, Y, rand_idx, nmb):
+        """The epoch's nmb steps as one mjrl_value_mlp_epoch call on the current
+        stream: the device model's parameters and the device optimizer's moments
+        are updated in place, then every step counter advances by nmb."""
+        dev = st["device"]
+        model, opt = st["model"], st["opt"]
+        params = list(model.parameters())
+        for p in params:   # a fresh optimizer has no state yet
+            sd = opt.state[p]
+            if not sd:
+                sd["step"] = torch.zeros((), dtype=torch.float32, device=dev)
+                sd["exp_avg"] = torch.zeros_like(p)
+                sd["exp_avg_sq"] = torch.zeros_like(p)
+        if X.dtype != torch.float32 or Y.dtype != torch.float32 or X.shape[1] != self.n + 4:
+            raise ValueError("the fused value fit takes f32 features [T][n + 4] and f32 returns")
+        X, Y, rand_idx = X.contiguous(), Y.contiguous(), rand_idx.contiguous()
+        K = _lib.calls()
+        if st.get("hip_scratch") is None:   # once per device mirror
+            nf = C.c_int64()
+            K.mjrl_value_mlp_scratch(self.n, self.batch_size, nf)
+            st["hip_scratch"] = torch.zeros(nf.value, dtype=torch.float32, device=dev)
+        net = _lib.ValueNet()
+        for i, p in enumerate(params):
+            net.p[i] = p.data_ptr()
+            net.exp_avg[i] = opt.state[p]["exp_avg"].data_ptr()
+            net.exp_avg_sq[i] = opt.state[p]["exp_avg_sq"].data_ptr()
+        g = opt.param_groups[0]
+        hp = _lib.Adam(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                       int(opt.state[params[0]]["step"].item()))
+        with torch.cuda.device(dev):
+            K.mjrl_value_mlp_epoch(X, Y, X.shape[0], self.n, rand_idx, nmb, self.batch_size, net, hp,
+                                   st["hip_scratch"], None, None, _lib.stream_ptr(torch.cuda.current_stream(dev)))
+        for p in params:
+            opt.state[p]["step"] += nmb
 
     def _epoch_sharded(self, st, X, Y, perm, lo, N_local, comm):
         """Data-parallel minibatches: this rank's members of each global minibatch
