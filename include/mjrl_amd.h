@@ -540,6 +540,58 @@ int mjrl_value_mlp_epoch(const float* X, const float* Y, int64_t T, int32_t n, c
                          int32_t bs, const mjrl_value_net* net, const mjrl_adam* hp, float* scratch, float* grad_out,
                          float* loss_out, void* stream);
 
+/* ---- PPO's and BC's minibatch Adam steps on the Gaussian MLP policy (mjrl/algos/ppo_clip.py:47-54,
+ * 89-95; behavior_cloning.py:39-63) ----
+ * The policy Linear(n, h0) - tanh - Linear(h0, h1) - tanh - Linear(h1, m) with log_std [m] and
+ * its Adam state, device pointers in torch's parameter order W0 [h0][n], b0 [h0], W1 [h1][h0],
+ * b1 [h1], W2 [m][h1], b2 [m], log_std [m] (actual sizes, nothing padded). */
+typedef struct mjrl_policy_net {
+    float* p[7];              /* the parameters */
+    float* exp_avg[7];        /* Adam's first moments, the parameters' shapes */
+    float* exp_avg_sq[7];     /* Adam's second moments */
+} mjrl_policy_net;
+#define MJRL_POLICY_FIT_BC 0   /* L = -(1/bs) sum LL_i */
+#define MJRL_POLICY_FIT_PPO 1  /* L = -(1/bs) sum min(LR_i adv_i, clamp(LR_i, 1 - clip, 1 + clip) adv_i) */
+/* The rows a call trains on and the loss.  obs [T][n], act [T][m], adv [T] (PPO; BC never
+ * reads it), the policy's transformations in_shift / in_scale [n], out_shift / out_scale [m]
+ * (mean = net((obs - in_shift) / (in_scale + 1e-8)) out_scale + out_shift), all f32 device
+ * pointers.  PPO's LR_i = exp(LL_i - LLold_i) takes LLold from exactly one of ll_old [T] (the
+ * old parameters are fixed during the call) and old_log_std [m] (the old mean network IS the
+ * new one: LLold_i is the step's own mean under old_log_std, with no gradient through it). */
+typedef struct mjrl_policy_fit_data {
+    const float *obs, *act, *adv, *ll_old, *old_log_std;
+    const float *in_shift, *in_scale, *out_shift, *out_scale;
+    int64_t T;
+    int32_t n, m, h0, h1;     /* 1 <= m, h0, h1 <= 64 */
+    int32_t kind;             /* MJRL_POLICY_FIT_BC / _PPO */
+    double clip;              /* PPO's clip coefficient */
+} mjrl_policy_fit_data;
+/* floats of scratch for one net (the last step's loss; the step's tiles live in LDS).
+ * MJRL_EINVAL for n <= 0, m / h0 / h1 outside 1..64, bs outside 1..64 or a null result. */
+int mjrl_policy_fit_scratch(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int64_t* floats);
+/* nmb minibatch Adam steps, enqueued on `stream`: step k trains on rows idx[k*bs .. k*bs+bs)
+ * (idx: device int64 [nmb][bs]; an entry outside [0, T) masks its row: it adds nothing to the
+ * gradient, which still divides by bs, and nothing of the row arrays is read for it).  The
+ * gradient is torch autograd's (elementwise min / clamp: a row whose LR lies inside the closed
+ * clip range passes its whole gradient, a clipped row none); Adam is torch's single-tensor
+ * formula (weight decay added to the gradient), step k with bias corrections
+ * 1 - beta^(step0 + k + 1) formed on the host in fp64 from the step number alone.
+ * net: the parameters and moments, updated in place.  scratch: mjrl_policy_fit_scratch floats.
+ * steps_per_launch: steps one launch runs (one workgroup owns the chain of steps); 0 is the
+ * default, 128, which is also the most a launch takes (a launch stays in the milliseconds).
+ * grad_out: null or [nmb][d], step k's minibatch gradient before weight decay, in torch
+ * parameter order (d = h0 n + h0 + h1 h0 + h1 + m h1 + m + m).  loss_out: null or [nmb].
+ * Exact-f32 MFMA, every sum in one fixed order, no atomics: the same state and arguments give
+ * the same bits, however nmb steps are split over calls (step0 advanced) and launches.  Never
+ * allocates, never synchronises.  MJRL_EINVAL before any launch for a null data, sizes outside
+ * the ranges above (n above 2^24), bs outside 1..64, a negative T, nmb, steps_per_launch or
+ * step0, an unknown kind, a PPO call with neither or both of ll_old and old_log_std, and,
+ * when nmb > 0, a null idx, net, hp, scratch, obs, act, transformation vector, adv (PPO) or a
+ * null pointer inside net; nmb == 0 is MJRL_OK without a launch. */
+int mjrl_policy_fit_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+                          const mjrl_policy_net* net, const mjrl_adam* hp, float* scratch, int32_t steps_per_launch,
+                          float* grad_out, float* loss_out, void* stream);
+
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----
  * dst[rows][n] = float(src) (round to nearest, as torch .float()), and when cmin /

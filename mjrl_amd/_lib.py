@@ -51,6 +51,22 @@ class ValueNet(C.Structure):
     _fields_ = [("p", C.c_void_p * 6), ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6)]
 
 
+class PolicyNet(C.Structure):
+    """mjrl_policy_net: the Gaussian MLP policy's parameters and Adam moments, torch order."""
+    _fields_ = [("p", C.c_void_p * 7), ("exp_avg", C.c_void_p * 7), ("exp_avg_sq", C.c_void_p * 7)]
+
+
+class PolicyFitData(C.Structure):
+    """mjrl_policy_fit_data"""
+    _fields_ = [(k, C.c_void_p) for k in ("obs", "act", "adv", "ll_old", "old_log_std", "in_shift", "in_scale",
+                                          "out_shift", "out_scale")] + \
+               [("T", C.c_int64), ("n", C.c_int32), ("m", C.c_int32), ("h0", C.c_int32), ("h1", C.c_int32),
+                ("kind", C.c_int32), ("clip", C.c_double)]
+
+
+POLICY_FIT_BC, POLICY_FIT_PPO = 0, 1   # MJRL_POLICY_FIT_BC / _PPO
+
+
 class Adam(C.Structure):
     """mjrl_adam"""
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
@@ -130,6 +146,9 @@ SIGNATURES = {
     "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
     "mjrl_value_mlp_scratch": [I32, I32, C.POINTER(I64)],
     "mjrl_value_mlp_epoch": [P, P, I64, I32, P, I64, I32, C.POINTER(ValueNet), C.POINTER(Adam), P, P, P, P],
+    "mjrl_policy_fit_scratch": [I32, I32, I32, I32, I32, C.POINTER(I64)],
+    "mjrl_policy_fit_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(PolicyNet), C.POINTER(Adam), P, I32,
+                              P, P, P],
     "mjrl_build_flags": [],
     "mjrl_host_stage_f64": [P, I64, I32, P, P, P],
     "mjrl_host_stage_f32": [P, I64, I32, P, P, P],

@@ -15,7 +15,14 @@ loss, backward, the optimizer step — is captured once as a hipGraph and replay
 per minibatch (capturable Adam); the minibatch indices come from numpy's global
 RNG in the reference's order, drawn for a whole epoch up front and uploaded in one
 copy.  Optimizers without a capturable mode run the same step eagerly.
+
+fit_backend = "hip" on BC / PPO (opt-in) replaces the graph replays of an epoch by
+one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on the same device
+parameters and the device optimizer's moments: DeviceTrainer.fused_epoch, limits
+in check_fit_backend.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -191,6 +198,92 @@ class DeviceTrainer:
                                 v.zero_()
         self._graphs[gkey] = (graph, idx)
         return self._graphs[gkey]
+
+
+    # ---- the fused route (fit_backend = "hip") -------------------------------------------
+    def fused_epoch(self, kind, obs, act, idx_batches, adv=None, ll_old=None, old_log_std=None, clip=0.0):
+        """epoch()'s steps as one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on
+        the current stream: self.params and the device optimizer's exp_avg /
+        exp_avg_sq are updated in place, then every step counter advances by nmb.
+        kind: "bc" or "ppo"; obs / act / adv / ll_old: this call's f32 device rows;
+        old_log_std: PPO's aliased form (PPO._old_on_device) instead of ll_old."""
+        from .. import _lib
+        nmb, bs = int(idx_batches.shape[0]), int(idx_batches.shape[1])
+        if nmb == 0:
+            return
+        dev = self.device
+        for p in self.params:   # a fresh optimizer has no state yet
+            sd = self.opt.state[p]
+            if "exp_avg" not in sd:
+                sd["step"] = torch.zeros((), dtype=torch.float32, device=dev)
+                sd["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                sd["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        rows = [t for t in (obs, act, adv, ll_old, old_log_std) if t is not None]
+        if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev for t in rows) \
+                or obs.shape[1] != self.policy.n or act.shape[1] != self.policy.m:
+            raise ValueError("the fused policy fit takes contiguous f32 rows obs [T][n], act [T][m] on the trainer's device")
+        idx_batches = idx_batches.contiguous()
+        K = _lib.calls()
+        if getattr(self, "_hip_scratch", None) is None:
+            nf = C.c_int64()
+            K.mjrl_policy_fit_scratch(self.policy.n, self.policy.m, self.policy.hidden[0], self.policy.hidden[1], bs, nf)
+            self._hip_scratch = torch.zeros(nf.value, dtype=torch.float32, device=dev)
+        net = _lib.PolicyNet()
+        for i, p in enumerate(self.params):
+            st = self.opt.state[p]
+            net.p[i], net.exp_avg[i], net.exp_avg_sq[i] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        data = _lib.PolicyFitData(ptr(obs), ptr(act), ptr(adv), ptr(ll_old), ptr(old_log_std),
+                                  *[t.data_ptr() for t in self._tf], int(obs.shape[0]), self.policy.n, self.policy.m,
+                                  self.policy.hidden[0], self.policy.hidden[1],
+                                  _lib.POLICY_FIT_PPO if kind == "ppo" else _lib.POLICY_FIT_BC, float(clip))
+        g = self.opt.param_groups[0]
+        step = self.opt.state[self.params[0]]["step"]
+        hp = _lib.Adam(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                       int(step.item() if torch.is_tensor(step) else step))
+        with torch.cuda.device(dev):
+            K.mjrl_policy_fit_epoch(data, idx_batches, nmb, bs, net, hp, self._hip_scratch, 0, None, None,
+                                    _lib.stream_ptr(torch.cuda.current_stream(dev)))
+        for p in self.params:
+            st = self.opt.state[p]
+            if torch.is_tensor(st["step"]):
+                st["step"] += nmb
+            else:
+                st["step"] = st["step"] + nmb
+
+
+FIT_BACKENDS = ("torch", "hip")
+HIP_MAX_BATCH = 64    # rows of a minibatch the fused kernel holds (csrc/policy_fit.hip)
+HIP_MAX_WIDTH = 64    # its largest hidden / action width
+
+
+def check_fit_backend(who, backend, policy, optimizer, mb_size, device):
+    """The fused route's limits, each a ValueError naming it, before anything
+    touches the GPU library.  Returns True when the backend is "hip"."""
+    if backend not in FIT_BACKENDS:
+        raise ValueError("%s.fit_backend must be one of %s, not %r" % (who, FIT_BACKENDS, backend))
+    if backend != "hip":
+        return False
+    pre = '%s.fit_backend = "hip"' % who
+    if not 1 <= int(mb_size) <= HIP_MAX_BATCH:
+        raise ValueError("%s takes minibatches of 1..%d rows, not %d" % (pre, HIP_MAX_BATCH, mb_size))
+    hidden = policy.hidden
+    if hidden is None:
+        raise ValueError("%s trains the Gaussian MLP policy (two hidden layers), not a LinearPolicy" % pre)
+    if len(hidden) != 2 or not all(1 <= int(h) <= HIP_MAX_WIDTH for h in hidden) or not 1 <= policy.m <= HIP_MAX_WIDTH:
+        raise ValueError("%s takes two hidden layers and an action width of 1..%d units each, not %r / %d"
+                         % (pre, HIP_MAX_WIDTH, tuple(hidden), policy.m))
+    if type(optimizer) is not torch.optim.Adam:
+        raise ValueError("%s takes a torch.optim.Adam optimizer, not %s" % (pre, type(optimizer).__name__))
+    if len(optimizer.param_groups) != 1:
+        raise ValueError("%s takes an Adam optimizer with one parameter group, not %d"
+                         % (pre, len(optimizer.param_groups)))
+    g = optimizer.param_groups[0]
+    if g.get("amsgrad", False) or g.get("maximize", False):
+        raise ValueError("%s takes Adam with amsgrad=False and maximize=False" % pre)
+    if default_device(device).type != "cuda":
+        raise ValueError("%s runs on the GPU, not on the %s trainer device" % (pre, default_device(device)))
+    return True
 
 
 def choice_batches(num_samples, mb_size, device):

@@ -11,6 +11,9 @@ once after, draws int(N / batch_size) minibatches of np.random.choice(N,
 batch_size) per epoch from numpy's global RNG, and ends with
 set_param_values(params, set_new=True, set_old=True) (the log_std clamp).
 The expert rows are staged to the device once per train() call.
+fit_backend = "hip" (opt-in, per instance or on the class) runs the minibatch
+steps as the fused kernel of csrc/policy_fit.hip instead (batch_size <= 64, MLP
+policies up to 64 units wide).
 """
 import logging
 import time as timer
@@ -19,12 +22,16 @@ import numpy as np
 import torch
 
 from ..utils.logger import DataLog
-from ._device_sgd import DeviceTrainer, choice_batches, default_device
+from ._device_sgd import DeviceTrainer, check_fit_backend, choice_batches, default_device
 
 logging.disable(logging.CRITICAL)
 
 
 class BC:
+    # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
+    # csrc/policy_fit.hip (opt-in, per instance or on the class)
+    fit_backend = "torch"
+
     def __init__(self, expert_paths, policy, epochs=5, batch_size=64, lr=1e-3, optimizer=None, device=None):
         self.policy = policy
         self.expert_paths = expert_paths
@@ -68,6 +75,7 @@ class BC:
     def train(self):
         observations = np.concatenate([path["observations"] for path in self.expert_paths])
         actions = np.concatenate([path["actions"] for path in self.expert_paths])
+        hip = check_fit_backend("BC", self.fit_backend, self.policy, self.optimizer, self.mb_size, self._device)
         tr = self.trainer()
         tr.pull()
         O, A = self._stage(observations, actions, tr.device)
@@ -88,8 +96,11 @@ class BC:
             self.logger.log_kv("epoch", ep)
             self.logger.log_kv("loss", np.float32(full_loss()))
             self.logger.log_kv("time", timer.time() - ts)
-            tr.epoch(("bc", self._ncall), mb_loss,
-                     choice_batches(num_samples, self.mb_size, tr.device))
+            batches = choice_batches(num_samples, self.mb_size, tr.device)
+            if hip:
+                tr.fused_epoch("bc", O, A, batches)
+            else:
+                tr.epoch(("bc", self._ncall), mb_loss, batches)
         tr.push()
         params_after_opt = self.policy.get_param_values()
         self.policy.set_param_values(params_after_opt, set_new=True, set_old=True)

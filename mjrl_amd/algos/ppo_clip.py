@@ -14,7 +14,9 @@ needs), with the old log-likelihoods computed once for all rows when the old
 parameters are fixed during the call (see _old_on_device for when they are not).  surr_before / surr_after / kl_dist come
 from the HIP engine's forward / evaluation passes (CPI_surrogate, kl_old_new).
 train_step is BatchREINFORCE's (device GAE), handing the paths with their
-advantages to train_from_paths.  Single process: the minibatch order is global,
+advantages to train_from_paths.  fit_backend = "hip" (opt-in, per instance or on
+the class) runs the minibatch steps as the fused kernel of csrc/policy_fit.hip
+instead (mb_size <= 64, MLP policies up to 64 units wide).  Single process: the minibatch order is global,
 so a sharded PPO is not offered (comm must be local).
 """
 import time as timer
@@ -23,12 +25,16 @@ import numpy as np
 import torch
 
 from .batch_reinforce import BatchREINFORCE
-from ._device_sgd import DeviceTrainer, choice_batches
+from ._device_sgd import DeviceTrainer, check_fit_backend, choice_batches
 from ..utils.logger import DataLog
 
 
 class PPO(BatchREINFORCE):
     _poolable = False   # the minibatch order is global: one process, even with MJRL_AMD_DEVICES set
+    # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
+    # csrc/policy_fit.hip (opt-in, per instance or on the class)
+    fit_backend = "torch"
+
     def __init__(self, env, policy, baseline, clip_coef=0.2, epochs=10, mb_size=64, learn_rate=3e-4, seed=0,
                  save_logs=False, device=None, comm=None):
         super().__init__(env, policy, baseline, learn_rate=learn_rate, seed=seed, save_logs=save_logs,
@@ -76,9 +82,24 @@ class PPO(BatchREINFORCE):
                 out.append(o.data.to(tr.device))
         return out, aliased
 
+    def _aliasing(self):
+        """Per parameter tensor: do the old and the new policy share storage (see
+        _old_on_device)?  Host pointers only."""
+        return [o.data.data_ptr() == n.data.data_ptr() and o.data.shape == n.data.shape
+                for o, n in zip(self.policy.old_params, self.policy.trainable_params)]
+
+    def _check_backend(self):
+        hip = check_fit_backend("PPO", self.fit_backend, self.policy, self.optimizer, self.mb_size, self._device)
+        if hip and self._aliasing() not in ([False] * 7, [True] * 6 + [False]):
+            raise ValueError('PPO.fit_backend = "hip" takes old parameters that share no storage with the new ones, '
+                             "or the six mean-network tensors shared and log_std not (what set_param_values "
+                             "leaves), not %r" % (self._aliasing(),))
+        return hip
+
     def train_from_paths(self, paths):
         if self.comm().world_size > 1:
             raise NotImplementedError("PPO's minibatch order is global (ppo_clip.py:89-91): run it in one process")
+        hip = self._check_backend()
         observations = np.concatenate([path["observations"] for path in paths])
         actions = np.concatenate([path["actions"] for path in paths])
         advantages = np.concatenate([path["advantages"] for path in paths])
@@ -124,7 +145,12 @@ class PPO(BatchREINFORCE):
         # the captured step reads this call's O / A / ADV / LL_old: a new key per call
         self._ncall = getattr(self, "_ncall", 0) + 1
         for ep in range(self.epochs):
-            tr.epoch(("ppo", self._ncall), mb_loss, choice_batches(num_samples, self.mb_size, dev))
+            batches = choice_batches(num_samples, self.mb_size, dev)
+            if hip:
+                tr.fused_epoch("ppo", O, A, batches, adv=ADV, ll_old=None if aliased else LL_old,
+                               old_log_std=old_dev[-1].contiguous() if aliased else None, clip=c)
+            else:
+                tr.epoch(("ppo", self._ncall), mb_loss, batches)
         tr.push()
         params_after_opt = self.policy.get_param_values()
         surr_after = float(self.CPI_surrogate(observations, actions, advantages))

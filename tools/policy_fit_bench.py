@@ -1,0 +1,126 @@
+"""PPO.train_from_paths on synthetic paths with fit_backend "torch" (a captured graph
+of torch ops per minibatch step) against "hip" (csrc/policy_fit.hip), at two shapes:
+
+    swimmer   n = 8, m = 2, hidden (64, 64), 25 paths of 500 rows, class defaults
+              (10 epochs of 195 minibatches of 64 rows: 1,950 Adam steps a call)
+    humanoid  n = 376, m = 17, hidden (64, 64), 100 paths of 1000 rows, epochs = 2
+              (3,124 steps a call)
+
+    python tools/policy_fit_bench.py [--alternations 3] [--timeout 300] [--shapes swimmer,humanoid]
+
+The backends alternate: a warm-up pair whose times are dropped, then
+`--alternations` pairs.  Every run is a child process of its own under its own
+time limit (a run that fails or overruns ends the tool: nothing more is started
+on the GPU after it); the child calls train_from_paths once untimed (graph
+capture, code-object load; it also leaves the old and new mean networks sharing
+storage, the form every later iteration has), then times one call between two
+synchronisations, and within it the minibatch epochs alone.  Prints the medians
+and ranges as one JSON line.  Needs a GPU."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SHAPES = {   # n, m, paths, rows per path, PPO keyword arguments
+    "swimmer": (8, 2, 25, 500, {}),
+    "humanoid": (376, 17, 100, 1000, dict(epochs=2)),
+}
+
+
+def child(args):
+    import numpy as np
+    import torch
+    from mjrl_amd.algos import _device_sgd
+    from mjrl_amd.algos.ppo_clip import PPO
+    from mjrl_amd.policies.gaussian_mlp import MLP
+    from mjrl_amd.utils.gym_env import EnvSpec
+    n, m, npaths, H, kw = SHAPES[args.shape]
+    policy = MLP(EnvSpec(n, m, H, 1), hidden_sizes=(64, 64), seed=1, init_log_std=-0.5)
+    agent = PPO(None, policy, None, **kw)
+    agent.fit_backend = args.child
+    spent = [0.0]
+
+    def timed(fn):
+        def run(self, *a, **k):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(self, *a, **k)
+            torch.cuda.synchronize()
+            spent[0] += time.perf_counter() - t0
+        return run
+    _device_sgd.DeviceTrainer.epoch = timed(_device_sgd.DeviceTrainer.epoch)
+    _device_sgd.DeviceTrainer.fused_epoch = timed(_device_sgd.DeviceTrainer.fused_epoch)
+    times, epochs_s = [], []
+    for it in range(2):   # the first call warms up (not reported)
+        rs = np.random.RandomState(10 + it)
+        # actions around the fresh policy's mean (its last layer starts at 1e-2 of torch's init)
+        paths = [dict(observations=rs.randn(H, n), actions=0.6 * rs.randn(H, m), rewards=rs.randn(H),
+                      advantages=rs.randn(H)) for _ in range(npaths)]
+        np.random.seed(5 + it)
+        spent[0] = 0.0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        agent.train_from_paths(paths)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+        epochs_s.append(spent[0])
+    steps = agent.epochs * int(npaths * H / agent.mb_size)
+    theta = policy.get_param_values()
+    print(json.dumps(dict(backend=args.child, shape=args.shape, call_s=times[1], epochs_s=epochs_s[1],
+                          warmup_s=times[0], steps=steps, param_norm=float(np.linalg.norm(theta)),
+                          finite=bool(np.all(np.isfinite(theta))))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--alternations", type=int, default=3)
+    ap.add_argument("--timeout", type=float, default=300.0, help="seconds per run (one child process)")
+    ap.add_argument("--shapes", default="swimmer,humanoid")
+    ap.add_argument("--shape", default="swimmer", help=argparse.SUPPRESS)
+    ap.add_argument("--child", choices=("torch", "hip"), default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    res = dict(tool="policy_fit_bench", shapes={})
+    for shape in args.shapes.split(","):
+        runs = {"torch": [], "hip": []}
+        steps, norm = 0, {}
+        for pair in range(args.alternations + 1):
+            for backend in ("torch", "hip"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", backend, "--shape", shape]
+                try:
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
+                except subprocess.TimeoutExpired:
+                    sys.exit("policy_fit_bench: the %s run exceeded %g s; stopping" % (backend, args.timeout))
+                if r.returncode != 0:
+                    sys.stderr.write(r.stderr[-4000:])
+                    sys.exit("policy_fit_bench: the %s run failed (exit %d); stopping" % (backend, r.returncode))
+                out = json.loads(r.stdout.strip().splitlines()[-1])
+                if not out["finite"]:
+                    sys.exit("policy_fit_bench: the %s run left non-finite parameters; stopping" % backend)
+                steps, norm[backend] = out["steps"], out["param_norm"]
+                if pair > 0:   # pair 0 is the warm-up pair
+                    runs[backend].append((out["call_s"], out["epochs_s"]))
+
+        def summary(xs):
+            return dict(median=statistics.median(xs), min=min(xs), max=max(xs), runs=xs)
+        one = dict(steps=steps, param_norm=norm)
+        for k in ("torch", "hip"):
+            one[k + "_call_s"] = summary([c for c, _ in runs[k]])
+            one[k + "_epochs_s"] = summary([e for _, e in runs[k]])
+        one["us_per_step"] = {k: 1e6 * one[k + "_epochs_s"]["median"] / max(steps, 1) for k in ("torch", "hip")}
+        one["speedup_epochs"] = one["torch_epochs_s"]["median"] / one["hip_epochs_s"]["median"]
+        one["speedup_call"] = one["torch_call_s"]["median"] / one["hip_call_s"]["median"]
+        res["shapes"][shape] = one
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
