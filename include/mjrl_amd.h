@@ -317,6 +317,14 @@ int mjrl_policy_eval(const mjrl_shape* s, const mjrl_rows* rows, int64_t T_eval,
 int mjrl_policy_eval_if(const mjrl_shape* s, const mjrl_rows* rows, int64_t T_eval, const float* packed_theta_new,
                         const float* packed_theta_old, const float* out_shift, const float* out_scale,
                         const mjrl_scratch* sc, double* sums, const int32_t* skip, void* stream);
+/* Which kernel the eval pass over split-f16 rows launches from now on (a process-
+ * wide setting, read at launch or capture time): 1 = the pipelined k_kx_eval_pipe
+ * (the default), 0 = the serial k_kx EVAL instance; the two are bit-identical
+ * (A/B runs, tests).  on < 0 only asks.  Returns the previous setting. */
+int mjrl_eval_pipe(int32_t on);
+/* Workgroups of the eval pass over T_eval rows (its per-workgroup records in
+ * scratch rpart: [grid][2] doubles, surrogate and KL sums). */
+int mjrl_eval_grid(const mjrl_shape* s, int64_t T_eval);
 
 /* The two steps behind the composites above, for callers that time or overlap
  * them separately.  *_accumulate writes per-slice partial sums of every weight /

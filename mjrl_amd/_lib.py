@@ -109,6 +109,8 @@ SIGNATURES = {
     "mjrl_policy_fvp": [SP, C.POINTER(Rows), I64, P, P, P, C.POINTER(Scratch), P, P, P],
     "mjrl_policy_eval": [SP, C.POINTER(Rows), I64, P, P, P, P, C.POINTER(Scratch), P, P],
     "mjrl_policy_eval_if": [SP, C.POINTER(Rows), I64, P, P, P, P, C.POINTER(Scratch), P, P, P],
+    "mjrl_eval_pipe": [I32],
+    "mjrl_eval_grid": [SP, I64],
     "mjrl_vpg_accumulate": [SP, C.POINTER(Rows), P, P, P, C.POINTER(Scratch), P],
     "mjrl_vpg_accumulate_pack": [SP, C.POINTER(Rows), P, P, P, P, C.POINTER(Scratch), P],
     "mjrl_policy_vpg_pack": [SP, C.POINTER(Rows), P, P, P, P, C.POINTER(Scratch), P, P],
@@ -237,7 +239,8 @@ def check(rc, what):
 
 
 # entry points whose int result is an answer, not a status: no errcheck
-QUERIES = ("mjrl_fused_path", "mjrl_split_supported", "mjrl_build_flags", "mjrl_host_stage_avx512")
+QUERIES = ("mjrl_fused_path", "mjrl_split_supported", "mjrl_build_flags", "mjrl_host_stage_avx512",
+           "mjrl_eval_pipe", "mjrl_eval_grid")
 _CALLS = {}
 
 

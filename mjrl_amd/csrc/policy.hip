@@ -1161,6 +1161,7 @@ __global__ void __launch_bounds__(64) k_eval_final(const double* __restrict__ rp
 #include "fused.h"
 #include "ks.h"
 #include "kx.h"
+#include "kxe.h"
 
 namespace {
 
@@ -1367,6 +1368,36 @@ int launch_kx_t(const RowArgs& ra, const FOut& fo, int grid, hipStream_t st) {
     }
     hipLaunchKernelGGL(fn, dim3(grid), dim3(KT), L::bytes, st, ra, fo);
     return (int)hipGetLastError();
+}
+
+// The EVAL pass over split-f16 rows: k_kx_eval_pipe (kxe.h, the default) or the
+// serial k_kx<.., EVAL> (mjrl_eval_pipe(0)); the two are bit-identical.
+int g_eval_pipe = 1;
+
+template <int MP, int KG>
+int launch_kx_eval_pipe_t(const RowArgs& ra, int grid, hipStream_t st) {
+    using L = XELayout<MP, KG>;
+    auto fn = k_kx_eval_pipe<MP, KG>;
+    static bool attr = false;
+    if (!attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, L::bytes);
+        if (e != hipSuccess) return (int)e;
+        attr = true;
+    }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(KT), L::bytes, st, ra);
+    return (int)hipGetLastError();
+}
+
+int launch_kx_eval_pipe(const mjrl_shape* s, const RowArgs& ra, int grid, hipStream_t st) {
+    const int kg = s->np / 32;
+#define MJRL_K(MP_, KG_) \
+    if (s->mp == MP_ && kg == KG_) return launch_kx_eval_pipe_t<MP_, KG_>(ra, grid, st);
+#define MJRL_KN(MP_) MJRL_K(MP_, 4) MJRL_K(MP_, 8) MJRL_K(MP_, 12)
+    MJRL_KN(16)
+    MJRL_KN(32)
+#undef MJRL_KN
+#undef MJRL_K
+    return MJRL_ESHAPE;
 }
 
 // rows given as split-f16 (ra.xs) run the all-split kernel k_kx; f32 xhat the
@@ -1776,6 +1807,17 @@ int mjrl_fused_path(const mjrl_shape* s) { return s ? acc_path(s, 1) : 0; }
 
 int mjrl_split_supported(const mjrl_shape* s) { return s && ksx_supported(s) ? 1 : 0; }
 
+int mjrl_eval_pipe(int32_t on) {
+    const int was = g_eval_pipe;
+    if (on >= 0) g_eval_pipe = on != 0;
+    return was;
+}
+
+int mjrl_eval_grid(const mjrl_shape* s, int64_t T_eval) {
+    if (!s || T_eval < 0) return 0;
+    return ks_supported(s) ? ks_grid(T_eval) : row_grid(s, T_eval);
+}
+
 static int policy_eval(const mjrl_shape* s, const mjrl_rows* rows, int64_t T_eval, const float* packed_theta_new,
                        const float* packed_theta_old, const float* out_shift, const float* out_scale,
                        const mjrl_scratch* sc, double* sums, const int32_t* skip, void* stream);
@@ -1814,7 +1856,8 @@ static int policy_eval(const mjrl_shape* s, const mjrl_rows* rows, int64_t T_eva
     const bool ks = ks_supported(s);
     const int G = ks ? ks_grid(T_eval) : row_grid(s, T_eval);
     if (T_eval > 0) {
-        int e = ks ? launch_ks<EVAL>(s, ra, FOut{}, G, st) : launch_rows<EVAL>(s, ra, G, st);
+        int e = ks ? (ra.xs && g_eval_pipe ? launch_kx_eval_pipe(s, ra, G, st) : launch_ks<EVAL>(s, ra, FOut{}, G, st))
+                   : launch_rows<EVAL>(s, ra, G, st);
         if (e) return e;
     } else {
         hipMemsetAsync(sc->rpart, 0, sizeof(double) * 2 * G, st);

@@ -626,6 +626,9 @@ class DeviceBatch:
 
 # the forward pass assembles the split rows itself where it can (UpdateEngine._fused_pack)
 FUSED_PACK = os.environ.get("MJRL_AMD_FUSED_PACK", "1") != "0"
+# MJRL_AMD_EVAL_PIPE=0: the serial EVAL kernel instead of the pipelined one (A/B runs;
+# bit-identical results); unset: the library's setting (mjrl_eval_pipe) is left alone
+EVAL_PIPE = os.environ.get("MJRL_AMD_EVAL_PIPE")
 TRPO_DEVICE_TRIALS = int(os.environ.get("MJRL_AMD_TRPO_DEVICE_TRIALS", "4"))   # see UpdateEngine.trpo_device_trials
 GRAPH_AUTO_ROWS = 300_000   # UpdateEngine.graphs == "auto": replay graphs up to this many rows (125k-row shard: 2.03 -> 1.97 ms; 1M rows: eager 4 % faster)
 HIDDEN_WIDTHS = (32, 64, 128, 256)   # hidden widths the row kernels are built for
@@ -687,6 +690,8 @@ class UpdateEngine:
         wherever the kernels support it (mjrl_split_supported), f32 elsewhere."""
         self.lib = _lib.lib()   # the raw handle (tools/ time single entry points through it)
         self.K = _lib.calls()   # the checked handle every launch below goes through
+        if EVAL_PIPE is not None:
+            self.K.mjrl_eval_pipe(int(EVAL_PIPE != "0"))
         real = (0, 0) if hidden is None else (int(hidden[0]), int(hidden[1]))
         kh = kernel_hidden(int(n), int(m), hidden)
         self.shape = _lib.make_shape(int(n), int(m), *kh)

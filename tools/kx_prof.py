@@ -20,6 +20,9 @@ NAMES = ["publish", "P1 first layer", "P1 fold", "P2", "P3", "row pass", "P4", "
          "P6 xload", "P6 G0 split", "P6 gW0", "P6 gW1", "P6 gW2+bias"]
 
 
+PIPE_NAMES = [(9, "loop top"), (0, "fold store, publish t+1, loads (to barrier 1)"), (2, "fold tanh + P1 group 0"),
+              (3, "P2 + P1 group 1"), (4, "P3 + P1 group 2"), (5, "row pass + P1 group 3 (no barrier after)")]
+
 NPROF = 24
 
 
@@ -54,9 +57,15 @@ def main(T=1000000):
     torch.cuda.synchronize()
     res["FVP"] = read(lib) / 3
     print("FVP + gather: %.1f us per call (events)" % (e0.elapsed_time(e1) / 3 * 1e3))
+    lib.mjrl_eval_pipe(0)
     eng.eval_pass(th, T)
     torch.cuda.synchronize()
     res["EVAL"] = read(lib)
+    # the pipelined EVAL (csrc/kxe.h) has its own intervals: printed apart
+    lib.mjrl_eval_pipe(1)
+    eng.eval_pass(th, T)
+    torch.cuda.synchronize()
+    pipe = read(lib)
     print("cycles per tile (wave 0 of workgroup 0, ~%d tiles)" % tiles)
     print("%-16s" % "phase" + "".join("%10s" % k for k in res))
     for i, n in enumerate(NAMES):
@@ -67,6 +76,13 @@ def main(T=1000000):
                  (21, " col scales+bar"), (22, " image stores"), (23, " xhat load+bar"), (16, "tail")):
         print("%-16s" % n + "".join("%10.0f" % (r[i] / max(r[17], 1)) for r in res.values()))
     print("%-16s" % "tile loop" + "".join("%10.0f" % (r[:15].sum() / max(r[17], 1)) for r in res.values()))
+    print("pipelined EVAL (k_kx_eval_pipe), cycles per tile: each interval holds tile t's chain phase and one "
+          "group of tile t+1's first-layer products")
+    for i, n in PIPE_NAMES:
+        print("%-44s%10.0f" % (n, pipe[i] / tiles))
+    print("%-44s%10.0f" % ("total", pipe[:15].sum() / tiles))
+    print("%-44s%10.0f" % ("preamble + first tile's publish and P1", pipe[15] / max(pipe[17], 1)))
+    print("%-44s%10.0f" % ("tail", pipe[16] / max(pipe[17], 1)))
 
 
 if __name__ == "__main__":
