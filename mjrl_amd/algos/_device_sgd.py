@@ -21,13 +21,12 @@ one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on the same device
 parameters and the device optimizer's moments: DeviceTrainer.fused_epoch, limits
 in check_fit_backend.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .._capture import capture
+from .. import _device_fit as _fit
+from .._device_fit import FIT_BACKENDS, HIP_MAX_BATCH
 
 LOG_2PI = float(np.log(2 * np.pi))
 
@@ -61,25 +60,8 @@ class DeviceTrainer:
         with torch.no_grad():
             for d, c in zip(self.params, self.policy.trainable_params):
                 d.copy_(c.data)
-        cpu_state = self.cpu_opt.state
-        for d, c in zip(self.params, self.policy.trainable_params):
-            sc = cpu_state.get(c)
-            sd = self.opt.state[d]
-            if not sc:
-                for v in sd.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-                continue
-            for k, v in sc.items():
-                if torch.is_tensor(v):
-                    v = v.to(self.device, dtype=torch.float32 if k == "step" else v.dtype)
-                    if k in sd and torch.is_tensor(sd[k]) and sd[k].shape == v.shape:
-                        sd[k].copy_(v)
-                    else:
-                        sd[k] = v.clone()
-                else:
-                    sd[k] = torch.tensor(float(v), dtype=torch.float32, device=self.device) \
-                        if k == "step" and self.graphable else v
+        _fit.state_to_device(self.cpu_opt, self.policy.trainable_params, self.opt, self.params, self.device,
+                             self.graphable)
         for gd, gc in zip(self.opt.param_groups, self.cpu_opt.param_groups):
             for k, v in gc.items():
                 if k not in ("params", "capturable", "foreach", "fused", "differentiable"):
@@ -103,16 +85,7 @@ class DeviceTrainer:
         with torch.no_grad():
             for d, c in zip(self.params, self.policy.trainable_params):
                 c.data.copy_(d.detach().cpu())
-        for d, c in zip(self.params, self.policy.trainable_params):
-            sd = self.opt.state.get(d)
-            if not sd:
-                continue
-            sc = self.cpu_opt.state[c]
-            for k, v in sd.items():
-                if torch.is_tensor(v):
-                    sc[k] = torch.tensor(float(v.item())) if k == "step" else v.detach().cpu().clone()
-                else:
-                    sc[k] = v
+        _fit.state_to_cpu(self.cpu_opt, self.policy.trainable_params, self.opt, self.params)
 
     # ---- the policy on the device -----------------------------------------------
     def mean(self, obs, params=None):
@@ -170,35 +143,9 @@ class DeviceTrainer:
             loss_fn(idx).backward()
             self.opt.step()
 
-        # the optimizer state has to exist before capture: one warm-up step on a side
-        # stream, then the parameters and state it touched are restored
-        saved = [p.detach().clone() for p in self.params]
-        saved_state = {p: {k: v.clone() for k, v in self.opt.state[p].items() if torch.is_tensor(v)}
-                       for p in self.params if self.opt.state.get(p)}
-        try:
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                body()
-            torch.cuda.current_stream(dev).wait_stream(s)
-            graph = torch.cuda.CUDAGraph()
-            with capture(graph):
-                body()
-        finally:
-            with torch.no_grad():
-                for p, v in zip(self.params, saved):
-                    p.copy_(v)
-                for p in self.params:
-                    st = self.opt.state.get(p, {})
-                    for k, v in st.items():
-                        if torch.is_tensor(v):
-                            if p in saved_state and k in saved_state[p]:
-                                v.copy_(saved_state[p][k])
-                            else:
-                                v.zero_()
+        graph = _fit.capture_step(body, self.params, self.opt, dev)
         self._graphs[gkey] = (graph, idx)
         return self._graphs[gkey]
-
 
     # ---- the fused route (fit_backend = "hip") -------------------------------------------
     def fused_epoch(self, kind, obs, act, idx_batches, adv=None, ll_old=None, old_log_std=None, clip=0.0):
@@ -212,49 +159,29 @@ class DeviceTrainer:
         if nmb == 0:
             return
         dev = self.device
-        for p in self.params:   # a fresh optimizer has no state yet
-            sd = self.opt.state[p]
-            if "exp_avg" not in sd:
-                sd["step"] = torch.zeros((), dtype=torch.float32, device=dev)
-                sd["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                sd["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        _fit.ensure_adam_state(self.opt, self.params, dev)   # a fresh optimizer has no state yet
         rows = [t for t in (obs, act, adv, ll_old, old_log_std) if t is not None]
         if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev for t in rows) \
                 or obs.shape[1] != self.policy.n or act.shape[1] != self.policy.m:
             raise ValueError("the fused policy fit takes contiguous f32 rows obs [T][n], act [T][m] on the trainer's device")
         idx_batches = idx_batches.contiguous()
         K = _lib.calls()
-        if getattr(self, "_hip_scratch", None) is None:
-            nf = C.c_int64()
-            K.mjrl_policy_fit_scratch(self.policy.n, self.policy.m, self.policy.hidden[0], self.policy.hidden[1], bs, nf)
-            self._hip_scratch = torch.zeros(nf.value, dtype=torch.float32, device=dev)
-        net = _lib.PolicyNet()
-        for i, p in enumerate(self.params):
-            st = self.opt.state[p]
-            net.p[i], net.exp_avg[i], net.exp_avg_sq[i] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        self._hip_scratch = _fit.scratch(getattr(self, "_hip_scratch", None), K.mjrl_policy_fit_scratch,
+                                         (self.policy.n, self.policy.m, *self.policy.hidden, bs), dev)
+        net = _fit.fill_net(_lib.PolicyNet(), self.opt, self.params)
         ptr = lambda t: None if t is None else t.data_ptr()
         data = _lib.PolicyFitData(ptr(obs), ptr(act), ptr(adv), ptr(ll_old), ptr(old_log_std),
                                   *[t.data_ptr() for t in self._tf], int(obs.shape[0]), self.policy.n, self.policy.m,
                                   self.policy.hidden[0], self.policy.hidden[1],
                                   _lib.POLICY_FIT_PPO if kind == "ppo" else _lib.POLICY_FIT_BC, float(clip))
-        g = self.opt.param_groups[0]
-        step = self.opt.state[self.params[0]]["step"]
-        hp = _lib.Adam(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                       int(step.item() if torch.is_tensor(step) else step))
+        hp = _fit.adam_hp(self.opt, self.params)
         with torch.cuda.device(dev):
             K.mjrl_policy_fit_epoch(data, idx_batches, nmb, bs, net, hp, self._hip_scratch, 0, None, None,
                                     _lib.stream_ptr(torch.cuda.current_stream(dev)))
-        for p in self.params:
-            st = self.opt.state[p]
-            if torch.is_tensor(st["step"]):
-                st["step"] += nmb
-            else:
-                st["step"] = st["step"] + nmb
+        _fit.advance_steps(self.opt, self.params, nmb)
 
 
-FIT_BACKENDS = ("torch", "hip")
-HIP_MAX_BATCH = 64    # rows of a minibatch the fused kernel holds (csrc/policy_fit.hip)
-HIP_MAX_WIDTH = 64    # its largest hidden / action width
+HIP_MAX_WIDTH = 64    # the fused kernel's largest hidden / action width (csrc/policy_fit.hip)
 
 
 def check_fit_backend(who, backend, policy, optimizer, mb_size, device):

@@ -30,17 +30,13 @@ model's own parameters and the device optimizer's moments, the same permutation
 buffer, batch_size <= 64.  The sharded fit stays on torch
 whatever the attribute says.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import _device_fit as _fit
 from .. import _lib
-from .._capture import capture
-
-FIT_BACKENDS = ("torch", "hip")
-HIP_MAX_BATCH = 64   # rows of a minibatch the fused kernels hold (csrc/value_fit.hip)
+from .._device_fit import FIT_BACKENDS, HIP_MAX_BATCH
 
 
 def _features_np(paths, n):
@@ -115,23 +111,7 @@ class MLPBaseline:
         with torch.no_grad():
             for pd, pc in zip(model.parameters(), self.model.parameters()):
                 pd.copy_(pc.data)
-        # Adam state: CPU optimizer -> device optimizer (same parameter order)
-        for pd, pc in zip(model.parameters(), self.model.parameters()):
-            sc = self.optimizer.state.get(pc)
-            sd = opt.state[pd]
-            if not sc:
-                if sd:
-                    sd["step"].zero_()
-                    sd["exp_avg"].zero_()
-                    sd["exp_avg_sq"].zero_()
-                continue
-            if not sd:
-                sd["step"] = torch.zeros((), dtype=torch.float32, device=dev)
-                sd["exp_avg"] = torch.zeros_like(pd)
-                sd["exp_avg_sq"] = torch.zeros_like(pd)
-            sd["step"].copy_(torch.as_tensor(float(sc["step"])))
-            sd["exp_avg"].copy_(sc["exp_avg"])
-            sd["exp_avg_sq"].copy_(sc["exp_avg_sq"])
+        _fit.state_to_device(self.optimizer, list(self.model.parameters()), opt, list(model.parameters()), dev, True)
         st["cpu_key"] = self._cpu_key()
         return st
 
@@ -157,14 +137,7 @@ class MLPBaseline:
             for pd, pc in zip(model.parameters(), self.model.parameters()):
                 pc.data.copy_(pd.detach().cpu())
         st["cpu_key"] = self._cpu_key()
-        for pd, pc in zip(model.parameters(), self.model.parameters()):
-            sd = opt.state.get(pd)
-            if not sd:
-                continue
-            sc = self.optimizer.state[pc]
-            sc["step"] = torch.tensor(float(sd["step"].item()))
-            sc["exp_avg"] = sd["exp_avg"].detach().cpu().clone()
-            sc["exp_avg_sq"] = sd["exp_avg_sq"].detach().cpu().clone()
+        _fit.state_to_cpu(self.optimizer, list(self.model.parameters()), opt, list(model.parameters()))
 
     def _step_graph(self, st, X, Y):
         """One minibatch Adam step as a captured hipGraph over static buffers:
@@ -184,34 +157,7 @@ class MLPBaseline:
             loss.backward()
             opt.step()
 
-        # the optimizer state must exist before capture; one warm-up step on a side
-        # stream, then restore the parameters / state it changed
-        saved = [p.detach().clone() for p in model.parameters()]
-        saved_state = {p: {k: v.clone() for k, v in opt.state[p].items()} for p in model.parameters()
-                       if opt.state.get(p)}
-        try:
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                body()
-            torch.cuda.current_stream(dev).wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with capture(g):
-                body()
-        finally:
-            # restored whether or not the capture succeeded (a failed capture falls
-            # back to eager steps, which must start from the untouched state)
-            with torch.no_grad():
-                for p, v in zip(model.parameters(), saved):
-                    p.copy_(v)
-                for p in model.parameters():
-                    if p in saved_state:
-                        for k, v in saved_state[p].items():
-                            opt.state[p][k].copy_(v)
-                    else:
-                        for k, v in opt.state[p].items():
-                            if torch.is_tensor(v):
-                                v.zero_()
+        g = _fit.capture_step(body, list(model.parameters()), opt, dev)
         st.update(graph=g, gkey=key, idx=idx)
         return st
 
@@ -325,33 +271,18 @@ class MLPBaseline:
         dev = st["device"]
         model, opt = st["model"], st["opt"]
         params = list(model.parameters())
-        for p in params:   # a fresh optimizer has no state yet
-            sd = opt.state[p]
-            if not sd:
-                sd["step"] = torch.zeros((), dtype=torch.float32, device=dev)
-                sd["exp_avg"] = torch.zeros_like(p)
-                sd["exp_avg_sq"] = torch.zeros_like(p)
+        _fit.ensure_adam_state(opt, params, dev)   # a fresh optimizer has no state yet
         if X.dtype != torch.float32 or Y.dtype != torch.float32 or X.shape[1] != self.n + 4:
             raise ValueError("the fused value fit takes f32 features [T][n + 4] and f32 returns")
         X, Y, rand_idx = X.contiguous(), Y.contiguous(), rand_idx.contiguous()
         K = _lib.calls()
-        if st.get("hip_scratch") is None:   # once per device mirror
-            nf = C.c_int64()
-            K.mjrl_value_mlp_scratch(self.n, self.batch_size, nf)
-            st["hip_scratch"] = torch.zeros(nf.value, dtype=torch.float32, device=dev)
-        net = _lib.ValueNet()
-        for i, p in enumerate(params):
-            net.p[i] = p.data_ptr()
-            net.exp_avg[i] = opt.state[p]["exp_avg"].data_ptr()
-            net.exp_avg_sq[i] = opt.state[p]["exp_avg_sq"].data_ptr()
-        g = opt.param_groups[0]
-        hp = _lib.Adam(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                       int(opt.state[params[0]]["step"].item()))
+        st["hip_scratch"] = _fit.scratch(st.get("hip_scratch"), K.mjrl_value_mlp_scratch, (self.n, self.batch_size), dev)
+        net = _fit.fill_net(_lib.ValueNet(), opt, params)
+        hp = _fit.adam_hp(opt, params)
         with torch.cuda.device(dev):
             K.mjrl_value_mlp_epoch(X, Y, X.shape[0], self.n, rand_idx, nmb, self.batch_size, net, hp,
                                    st["hip_scratch"], None, None, _lib.stream_ptr(torch.cuda.current_stream(dev)))
-        for p in params:
-            opt.state[p]["step"] += nmb
+        _fit.advance_steps(opt, params, nmb)
 
     def _epoch_sharded(self, st, X, Y, perm, lo, N_local, comm):
         """Data-parallel minibatches: this rank's members of each global minibatch

@@ -37,13 +37,11 @@
 // Arithmetic: products on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fma chain,
 // one accumulator per output tile), every sum in one fixed order, no atomic: the same
 // state and arguments give the same bits, however the steps are split over launches
-// and calls.  Adam is value_fit.hip's adam_step, the bias corrections of step t formed
+// and calls.  Adam is fit.h's adam_step, the bias corrections of step t formed
 // on the host in f64 from t alone.  Rows bs .. 63 and a row whose index is outside
 // [0, T) are masked: nothing of obs / act / adv / ll_old is read for them, their
 // dL/dLL is 0, the mean still divides by bs.
-#include <math.h>
-
-#include "common.h"
+#include "fit.h"
 
 using namespace mjrl;
 
@@ -80,11 +78,6 @@ constexpr int PF_NPROF = 14;
     } while (0)
 #endif
 
-struct AdamK {
-    double omb1, beta2, omb2, wd;     // 1 - beta1, beta2, 1 - beta2, weight decay
-    float step_size, bc2s, eps;       // lr / bc1, sqrt(bc2), eps
-};
-
 struct PfitArgs {
     const float *obs, *act, *adv, *ll_old, *old_ls;
     const float *in_shift, *in_scale, *out_shift, *out_scale;
@@ -101,59 +94,9 @@ struct PfitArgs {
     int n, na, h0, h1, bs, kind, nsteps;   // na: the action width m
     int vx, vw0, vw1, vw2;            // 16-byte loads of obs rows / W0 / W1 / W2 rows allowed
     float clip_lo, clip_hi;           // float(1 - c), float(1 + c)
-    double omb1, beta2, omb2, wd;
-    float eps;
-    float step_size[PF_SPL], bc2s[PF_SPL];
+    AdamK hp;                         // the step-independent part
+    float step_size[PF_SPL], bc2s[PF_SPL];   // hp's other two fields for each step of this launch
 };
-
-// one element's Adam step from its loaded parameter and moments; g is the minibatch
-// gradient before weight decay (value_fit.hip's, unchanged in arithmetic)
-__device__ __forceinline__ void adam_step(float p0, float m0, float v0, float g, const AdamK& h, float& p1, float& m1,
-                                          float& v1) {
-    const double gd = (double)g + h.wd * (double)p0;
-    m1 = (float)((double)m0 + (gd - (double)m0) * h.omb1);
-    v1 = (float)(h.beta2 * (double)v0 + h.omb2 * (gd * gd));
-    const float denom = sqrtf(v1) / h.bc2s + h.eps;
-    p1 = p0 - h.step_size * (m1 / denom);
-}
-
-// W[row][k .. k + 3] of a [rows][K] matrix, zero for row >= rows and past K
-__device__ __forceinline__ float4 ldw4(const float* W, int rows, int K, int row, int k, bool vec) {
-    const float* const p = W + (size_t)(row < rows ? row : rows - 1) * K;
-    float4 r;
-    if (vec) {   // K % 4 == 0, k % 4 == 0: all four inside or all four outside
-        r = *reinterpret_cast<const float4*>(p + (k < K ? k : K - 4));
-        if (k >= K || row >= rows) r = float4{0.f, 0.f, 0.f, 0.f};
-        return r;
-    }
-    const int l = K - 1;
-    r.x = p[k < l ? k : l];
-    r.y = p[k + 1 < l ? k + 1 : l];
-    r.z = p[k + 2 < l ? k + 2 : l];
-    r.w = p[k + 3 < l ? k + 3 : l];
-    const bool in = row < rows;
-    r.x = in && k < K ? r.x : 0.f;
-    r.y = in && k + 1 < K ? r.y : 0.f;
-    r.z = in && k + 2 < K ? r.z : 0.f;
-    r.w = in && k + 3 < K ? r.w : 0.f;
-    return r;
-}
-
-// W[j .. j + 3][col] of a [rows][K] matrix (the transposed operand), zero outside
-__device__ __forceinline__ float4 ldwt4(const float* W, int rows, int K, int j, int col) {
-    const int c = col < K ? col : K - 1, l = rows - 1;
-    float4 r;
-    r.x = W[(size_t)(j < l ? j : l) * K + c];
-    r.y = W[(size_t)(j + 1 < l ? j + 1 : l) * K + c];
-    r.z = W[(size_t)(j + 2 < l ? j + 2 : l) * K + c];
-    r.w = W[(size_t)(j + 3 < l ? j + 3 : l) * K + c];
-    const bool in = col < K;
-    r.x = in && j < rows ? r.x : 0.f;
-    r.y = in && j + 1 < rows ? r.y : 0.f;
-    r.z = in && j + 2 < rows ? r.z : 0.f;
-    r.w = in && j + 3 < rows ? r.w : 0.f;
-    return r;
-}
 
 __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
     __shared__ __attribute__((aligned(16))) float Xs[PR * XLD];    // xhat, one chunk of columns
@@ -188,12 +131,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
     const int nchunk_f = (n + XCW - 1) / XCW;   // forward chunks
     const int nchunk_b = n / XCW + 1;           // backward chunks: the column of ones (col n) counts
 
-    AdamK hp;
-    hp.omb1 = a.omb1;
-    hp.beta2 = a.beta2;
-    hp.omb2 = a.omb2;
-    hp.wd = a.wd;
-    hp.eps = a.eps;
+    AdamK hp = a.hp;   // step_size / bc2s: the current step's, set below
 
     // the gathered, normalised X tile of chunk c: 8 threads per row, zero-filled to a multiple of 16 columns
     auto load_chunk = [&](int c) {
@@ -271,21 +209,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
             for (int i = 0; i < 4; ++i) {
                 const int unit = 16 * jub + 4 * q + i;
                 if (unit >= U) continue;
-                const float g = acc[i];
-                float p1, m1, v1;
-                adam_step(pm[i][0], pm[i][1], pm[i][2], g, hp, p1, m1, v1);
-                if (col < K) {
-                    const unsigned e = (unsigned)unit * K + col;
-                    if (grad) grad[gw + e] = g;
-                    pw[e] = p1;
-                    mw[e] = m1;
-                    vw[e] = v1;
-                } else {
-                    if (grad) grad[gb + unit] = g;
-                    pb[unit] = p1;
-                    mb[unit] = m1;
-                    vb[unit] = v1;
-                }
+                wgrad_tail(pm[i], acc[i], unit, K, col, hp, pw, mw, vw, pb, mb, vb, grad, gw, gb);
             }
         }
     };
@@ -613,11 +537,10 @@ int mjrl_policy_fit_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, 
     if (!data->obs || !data->act || !data->in_shift || !data->in_scale || !data->out_shift || !data->out_scale)
         return MJRL_EINVAL;
     if (data->kind == MJRL_POLICY_FIT_PPO && !data->adv) return MJRL_EINVAL;
-    for (int i = 0; i < 7; ++i)
-        if (!net->p[i] || !net->exp_avg[i] || !net->exp_avg_sq[i]) return MJRL_EINVAL;
+    PfitArgs a;
+    if (!net_ptrs(net, a.p, a.m, a.v)) return MJRL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int spl = steps_per_launch == 0 || steps_per_launch > PF_SPL ? PF_SPL : steps_per_launch;
-    PfitArgs a;
     a.obs = data->obs;
     a.act = data->act;
     a.adv = data->adv;
@@ -628,11 +551,6 @@ int mjrl_policy_fit_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, 
     a.out_shift = data->out_shift;
     a.out_scale = data->out_scale;
     a.T = data->T;
-    for (int i = 0; i < 7; ++i) {
-        a.p[i] = net->p[i];
-        a.m[i] = net->exp_avg[i];
-        a.v[i] = net->exp_avg_sq[i];
-    }
     a.scratch = scratch;
     a.scap = PF_SCRATCH;
     a.d = (int64_t)h0 * n + h0 + (int64_t)h1 * h0 + h1 + (int64_t)m * h1 + m + m;
@@ -649,19 +567,10 @@ int mjrl_policy_fit_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, 
     a.vw2 = h1 % 4 == 0 && al16(net->p[4]);
     a.clip_lo = (float)(1.0 - data->clip);
     a.clip_hi = (float)(1.0 + data->clip);
-    a.omb1 = 1.0 - hp->beta1;
-    a.beta2 = hp->beta2;
-    a.omb2 = 1.0 - hp->beta2;
-    a.wd = hp->weight_decay;
-    a.eps = (float)hp->eps;
+    a.hp = adam_consts(hp);
     for (int64_t k0 = 0; k0 < nmb; k0 += spl) {
         const int ns = (int)(nmb - k0 < spl ? nmb - k0 : spl);
-        for (int s = 0; s < ns; ++s) {
-            // a function of the absolute step number alone, whatever the split into launches
-            const double t = (double)(hp->step0 + k0 + s + 1);
-            a.step_size[s] = (float)(hp->lr / (1.0 - pow(hp->beta1, t)));
-            a.bc2s[s] = (float)sqrt(1.0 - pow(hp->beta2, t));
-        }
+        for (int s = 0; s < ns; ++s) adam_bias(hp, k0 + s, a.step_size[s], a.bc2s[s]);
         for (int s = ns; s < PF_SPL; ++s) a.step_size[s] = a.bc2s[s] = 1.f;
         a.nsteps = ns;
         a.idx = idx + k0 * bs;

@@ -38,15 +38,9 @@
 // padded to 64 rows; a padded row and a row whose index is outside [0, T) are
 // masked (nothing of X / Y is read for them, their dout is 0).
 //
-// Adam (torch's single-tensor formula): g' = g + wd p, m += (g' - m)(1 - beta1),
-// v = beta2 v + (1 - beta2) g'^2 evaluated in f64 and rounded once on the store
-// (an f32 evaluation cancels in m for g' near -9 m), then
-// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps) in f32 on the stored moments,
-// the bias corrections bc1 = 1 - beta1^t, bc2 = 1 - beta2^t formed on the host
-// in f64 for every step.
-#include <math.h>
-
-#include "common.h"
+// Adam, the operand loaders and the tail of an update job are fit.h's, shared with
+// policy_fit.hip.
+#include "fit.h"
 
 using namespace mjrl;
 
@@ -71,11 +65,6 @@ constexpr int TPR = SLICE_THREADS / VR;       // threads staging one row of the 
 constexpr int KS = SW / 4;            // forward half: waves splitting k (times four row blocks)
 constexpr int FG = XCW / 16 / KS;     // forward k groups of a wave per 384 columns
 
-struct AdamK {
-    double omb1, beta2, omb2, wd;     // 1 - beta1, beta2, 1 - beta2, weight decay
-    float step_size, bc2s, eps;       // lr / bc1, sqrt(bc2), eps
-};
-
 struct VfitArgs {
     const float* X;
     const float* Y;
@@ -92,38 +81,6 @@ struct VfitArgs {
     int F, bs, vec;                   // vec: 16-byte loads of X / W0 rows allowed
     AdamK hp;
 };
-
-// one element's Adam step from its loaded parameter and moments; g is the minibatch
-// gradient before weight decay
-__device__ __forceinline__ void adam_step(float p0, float m0, float v0, float g, const AdamK& h, float& p1, float& m1,
-                                          float& v1) {
-    const double gd = (double)g + h.wd * (double)p0;
-    m1 = (float)((double)m0 + (gd - (double)m0) * h.omb1);
-    v1 = (float)(h.beta2 * (double)v0 + h.omb2 * (gd * gd));
-    const float denom = sqrtf(v1) / h.bc2s + h.eps;
-    p1 = p0 - h.step_size * (m1 / denom);
-}
-
-// row[k .. k + 3], zero past F; branch-free (clamped addresses, then selects) so that a
-// run of them issues as one burst.  F >= 4.
-__device__ __forceinline__ float4 ld4(const float* row, int k, int F, bool vec) {
-    float4 r;
-    if (vec) {   // F % 4 == 0, k % 4 == 0: all four inside or all four outside
-        r = *reinterpret_cast<const float4*>(row + (k < F ? k : F - 4));
-        if (k >= F) r = float4{0.f, 0.f, 0.f, 0.f};
-        return r;
-    }
-    const int l = F - 1;
-    r.x = row[k < l ? k : l];
-    r.y = row[k + 1 < l ? k + 1 : l];
-    r.z = row[k + 2 < l ? k + 2 : l];
-    r.w = row[k + 3 < l ? k + 3 : l];
-    r.x = k < F ? r.x : 0.f;
-    r.y = k + 1 < F ? r.y : 0.f;
-    r.z = k + 2 < F ? r.z : 0.f;
-    r.w = k + 3 < F ? r.w : 0.f;
-    return r;
-}
 
 // float offset of step k's a0 in the scratch
 __device__ __forceinline__ int a0_off(int64_t k) { return (k & 1) ? A0_ODD : 0; }
@@ -327,21 +284,9 @@ __global__ void __launch_bounds__(SLICE_THREADS) k_vfit_slice(VfitArgs a) {
                 if (col <= K) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const unsigned unit = 16 * u + 4 * q + i, e = unit * K + col;
-                        const float g = acc[0][i] + acc[1][i];
-                        float p1, m1, v1;
-                        adam_step(pm[jj][i][0], pm[jj][i][1], pm[jj][i][2], g, a.hp, p1, m1, v1);
-                        if (col < K) {
-                            if (a.grad) (a.grad + jb.gw)[e] = g;
-                            jb.pw[e] = p1;
-                            jb.mw[e] = m1;
-                            jb.vw[e] = v1;
-                        } else {
-                            if (a.grad) (a.grad + jb.gb)[unit] = g;
-                            jb.pb[unit] = p1;
-                            jb.mb[unit] = m1;
-                            jb.vb[unit] = v1;
-                        }
+                        const unsigned unit = 16 * u + 4 * q + i;
+                        wgrad_tail(pm[jj][i], acc[0][i] + acc[1][i], unit, K, col, a.hp, jb.pw, jb.mw, jb.vw, jb.pb, jb.mb,
+                                   jb.vb, a.grad, jb.gw, jb.gb);
                     }
                 }
             }
@@ -530,40 +475,27 @@ int mjrl_value_mlp_epoch(const float* X, const float* Y, int64_t T, int32_t n, c
     if (n <= 0 || n > (1 << 24) || bs < 1 || bs > VR || T < 0 || nmb < 0) return MJRL_EINVAL;
     if (nmb == 0) return MJRL_OK;
     if (!X || !Y || !perm || !net || !hp || !scratch || hp->step0 < 0) return MJRL_EINVAL;
-    for (int i = 0; i < 6; ++i)
-        if (!net->p[i] || !net->exp_avg[i] || !net->exp_avg_sq[i]) return MJRL_EINVAL;
+    VfitArgs a;
+    if (!net_ptrs(net, a.p, a.m, a.v)) return MJRL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int F = n + 4;
     const int64_t d = (int64_t)VH * F + VH + (int64_t)VH * VH + VH + VH + 1;
-    VfitArgs a;
     a.X = X;
     a.Y = Y;
     a.T = T;
     a.perm = perm;
-    for (int i = 0; i < 6; ++i) {
-        a.p[i] = net->p[i];
-        a.m[i] = net->exp_avg[i];
-        a.v[i] = net->exp_avg_sq[i];
-    }
     a.scratch = scratch;
     a.scap = VSCRATCH;
     a.F = F;
     a.bs = bs;
     a.vec = F % 4 == 0 && ((uintptr_t)X | (uintptr_t)net->p[0]) % 16 == 0;
-    a.hp.omb1 = 1.0 - hp->beta1;
-    a.hp.beta2 = hp->beta2;
-    a.hp.omb2 = 1.0 - hp->beta2;
-    a.hp.wd = hp->weight_decay;
-    a.hp.eps = (float)hp->eps;
+    a.hp = adam_consts(hp);
     a.grad = nullptr;
     a.loss = nullptr;
     a.kU = a.kF = 0;
-    a.hp.step_size = a.hp.bc2s = 1.f;
     hipLaunchKernelGGL((k_vfit_slice<false, true>), dim3(VH / 16), dim3(SLICE_THREADS), 0, st, a);
     for (int64_t k = 0; k < nmb; ++k) {
-        const double t = (double)(hp->step0 + k + 1);
-        a.hp.step_size = (float)(hp->lr / (1.0 - pow(hp->beta1, t)));
-        a.hp.bc2s = (float)sqrt(1.0 - pow(hp->beta2, t));
+        adam_bias(hp, k, a.hp.step_size, a.hp.bc2s);
         a.grad = grad_out ? grad_out + k * d : nullptr;
         a.loss = loss_out ? loss_out + k : nullptr;
         a.kU = a.kF = k;
