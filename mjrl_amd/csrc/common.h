@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/mjrl_amd.h"
+#include "pow2_scale.h"
 
 #ifdef MJRL_KX_PROF
 // phase profile (profiling builds) of k_kx / k_fused: wave 0 of block 0 accumulates s_memtime cycles
@@ -90,22 +91,8 @@ __device__ __forceinline__ floatx4 mfma_x3(const half8& ah, const half8& al, con
     return mfma_h(al, bh, c);
 }
 
-constexpr int SPLIT_HR = 15;   // block max -> [2^(SPLIT_HR-1), 2^SPLIT_HR)
-
-// Power-of-two scale for a block whose max |value| is M: returns s = 2^(15-E) with
-// M * s in [2^14, 2^15) and sets inv = 1 / s = 2^(E-15) (s = inv = 1 for M == 0 /
-// non-finite; blocks below 2^-111 keep s = 2^126).
-__device__ __forceinline__ float pow2_scale(float M, float& inv) {
-    if (!(M > 0.f) || !(M < 3.0e38f)) {
-        inv = 1.f;
-        return 1.f;
-    }
-    int E;
-    frexpf(M, &E);
-    E = E < -111 ? -111 : E;
-    inv = ldexpf(1.f, E - SPLIT_HR);
-    return ldexpf(1.f, SPLIT_HR - E);
-}
+// SPLIT_HR = 15 (block max -> [2^(SPLIT_HR-1), 2^SPLIT_HR)) and pow2_scale, the
+// block's power-of-two scale, live in pow2_scale.h (no HIP dependency).
 
 // Split xhat rows (mjrl_rows.xs): column k carries xhat / xc[k] with xc[k] = 2^E the
 // power of two with colmax[k] 2^-E in [1/2, 1) over the batch (1 for an all-zero
@@ -182,17 +169,6 @@ __device__ __forceinline__ float mix_add_hi(unsigned h2, unsigned l2) {
     asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h2), "v"(l2));
     return r;
 }
-__device__ __forceinline__ float8v hilo8(const half8& hh, const half8& ll) {
-    const uint4v h = __builtin_bit_cast(uint4v, hh), l = __builtin_bit_cast(uint4v, ll);
-    float8v r;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        r[2 * p] = mix_add_lo(h[p], l[p]);
-        r[2 * p + 1] = mix_add_hi(h[p], l[p]);
-    }
-    return r;
-}
-
 __device__ __forceinline__ float8v load8(const float* p) {
     const float4 a = *reinterpret_cast<const float4*>(p);
     const float4 b = *reinterpret_cast<const float4*>(p + 4);
@@ -210,11 +186,24 @@ __device__ __forceinline__ float absmax8(const float8v& v) {
 // round trip): permlane16_swap(x, x) gives every lane {x[l], x[l ^ 16]} in
 // (lower group, upper group) order, permlane32_swap(x, x) {x[l], x[l ^ 32]}
 // likewise (checked by tools/permlane_check.hip).
+//
+// The maxima here are over absolute values (absmax8): non-negative floats, whose
+// order is the order of their bit patterns as unsigned integers.  umax_bits takes
+// the maximum there: one v_max_u32 per step, where fmaxf on a value that came out
+// of a lane swap or a DPP move costs two canonicalising v_max_f32 x, x, x first (the
+// compiler cannot see that the value is already canonical).  Same bits as fmaxf for
+// every pair of non-negative non-NaN floats.  A NaN is outside the contract: its
+// pattern is above every finite one, so an integer maximum carries it to the block
+// maximum (where pow2_scale answers (1, 1)), while fmaxf dropped it.
+__device__ __forceinline__ float umax_bits(float a, float b) {
+    const unsigned x = __float_as_uint(a), y = __float_as_uint(b);
+    return __uint_as_float(x > y ? x : y);
+}
 __device__ __forceinline__ float max_over_groups(float v) {
     const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+    const unsigned m = a[0] > a[1] ? a[0] : a[1];
+    const auto b = __builtin_amdgcn_permlane32_swap(m, m, false, false);
+    return __uint_as_float(b[0] > b[1] ? b[0] : b[1]);
 }
 
 // sum over the four 16-lane groups, the same fixed order in every lane

@@ -56,7 +56,8 @@ struct XLayout {
     static constexpr int oA0 = oG1T + H * LDT * 4;   // a0 image hi, lo
     static constexpr int oA1 = oA0 + 2 * AIMG;       // a1 image hi, lo
     static constexpr int oD0B = oA1 + 2 * AIMG;      // FVP: f32 [BT][LD] partial of observation half 1
-    static constexpr int bytes = oD0B + BT * LD * 4;
+    static constexpr int oBC = oD0B + BT * LD * 4;   // f32 [8 waves][16]: the row-scale broadcasts (bcast4)
+    static constexpr int bytes = oBC + (KT / 64) * 16 * 4;
     static_assert(bytes <= 160 * 1024, "LDS");
     static_assert(bytes >= 2 * KT * 8, "row_pass_final scratch");
     static constexpr int XPER = BT * NP / 4 / KT;
@@ -79,11 +80,12 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), CTRL, 0xf, 0xf, false));
 }
+// (v >= 0: the maximum on the bit patterns, common.h umax_bits)
 __device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_f<0xB1>(v));
-    v = fmaxf(v, dpp_f<0x4E>(v));
-    v = fmaxf(v, dpp_f<0x141>(v));
-    return fmaxf(v, dpp_f<0x140>(v));
+    v = umax_bits(v, dpp_f<0xB1>(v));
+    v = umax_bits(v, dpp_f<0x4E>(v));
+    v = umax_bits(v, dpp_f<0x141>(v));
+    return umax_bits(v, dpp_f<0x140>(v));
 }
 
 __device__ __forceinline__ half8 cat_tr(const short4v& a, const short4v& b) {
@@ -145,6 +147,47 @@ __device__ __forceinline__ void astore4(char* img, int f, int row0, const float 
     *reinterpret_cast<uint2v*>(img + off) = hb;
     *reinterpret_cast<uint2v*>(img + AIMG_BYTES + off) = lb;
 }
+// astore4, and om[rr] = 1 - a^2 of the a the image's readers reconstruct (aval4:
+// (hi + lo) / AHR, which is not always a[rr] itself: y - hi can need 12 bits and lo
+// keeps 11), in the one rounding of the fused multiply-add those readers' 1.f - av *
+// av contracts to: the bits P2 used to rebuild in each of a row block's four waves,
+// computed once by the lane that holds the pair
+__device__ __forceinline__ void astore4_om(char* img, int f, int row0, const float (&a)[4], float (&om)[4]) {
+    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+    typedef unsigned uint2v __attribute__((ext_vector_type(2)));
+    typedef float float4v __attribute__((ext_vector_type(4)));
+    const float v[4] = {a[0] * AHR, a[1] * AHR, a[2] * AHR, a[3] * AHR};
+    const float4v x = {v[0], v[1], v[2], v[3]};
+    const half4 h = __builtin_convertvector(x, half4);
+    const uint2v hb = __builtin_bit_cast(uint2v, h);
+    const uint2v lb = {mix_lo2(hb[0], v[0], v[1]), mix_lo2(hb[1], v[2], v[3])};
+    const int off = aoff(f, row0);
+    *reinterpret_cast<uint2v*>(img + off) = hb;
+    *reinterpret_cast<uint2v*>(img + AIMG_BYTES + off) = lb;
+    const float av[4] = {mix_add_lo(hb[0], lb[0]) * AHR_INV, mix_add_hi(hb[0], lb[0]) * AHR_INV,
+                         mix_add_lo(hb[1], lb[1]) * AHR_INV, mix_add_hi(hb[1], lb[1]) * AHR_INV};
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) om[rr] = __builtin_fmaf(-av[rr], av[rr], 1.f);
+}
+
+// The four scales an MFMA lane applies to its accumulator rows 4q .. 4q + 3, from the
+// per-row value `inv` that lane r of every 16-lane group holds for row r (the same in
+// all four groups: max_over_groups): one 4-byte write and one 16-byte read of this
+// wave's 64 bytes of LDS (scr), where __shfl(inv, 4q + rr) was four ds_bpermute and
+// four address registers held for the whole launch.  Wave-local: a wave's LDS
+// operations execute in order, so no barrier; the fence keeps the compiler from
+// moving the read over the write.
+__device__ __forceinline__ void bcast4(float* scr, float inv, int q, int r, float (&o)[4]) {
+    scr[r] = inv;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float4 t = *reinterpret_cast<const float4*>(scr + 4 * q);
+    o[0] = t.x;
+    o[1] = t.y;
+    o[2] = t.z;
+    o[3] = t.w;
+}
 
 // Dynamic left operand from an f32 [row][ld] buffer: rows rb*16 + r, K = 32*KS
 // columns, optionally times fold[k] (a column scale of the right operand);
@@ -172,13 +215,12 @@ __device__ __forceinline__ float adyn(const float* buf, int ld, int rb, int q, i
 // buffer: unit u = ub*16 + r, rows 8q..8q+7; scaled per (tile, unit); returns in
 // sc4[rr] the inverse scale of output row (unit) 4q + rr of the block.
 __device__ __forceinline__ void gdyn(const float* bufT, int ldt, int ub, int q, int r, half8& h, half8& l,
-                                     float (&sc4)[4]) {
+                                     float (&sc4)[4], float* scr) {
     const float8v v = load8(bufT + (ub * 16 + r) * ldt + 8 * q);
     float inv;
     const float s = pow2_scale(max_over_groups(absmax8(v)), inv);
     split8(v, s, h, l);
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) sc4[rr] = __shfl(inv, 4 * q + rr, 64);
+    bcast4(scr, inv, q, r, sc4);
 }
 
 // Split a [rows][64] f32 weight matrix (global, row-major, row stride 64) into an
@@ -278,6 +320,12 @@ __device__ __forceinline__ void wstore(const float (&v)[IR], char* img, int imgb
     }
 }
 
+// FVP P5 takes 1 - a0^2 from the registers P1 left it in (1) or rebuilds it from the
+// a0 image as FWD does (0: the A/B of profiles/r09a)
+#ifndef MJRL_KX_OM_REG
+#define MJRL_KX_OM_REG 1
+#endif
+constexpr bool KX_OM_REG = MJRL_KX_OM_REG;
 #ifdef MJRL_KX_ABL_NOCHAIN
 constexpr bool KX_ABL_NOCHAIN = true;    // timing ablation only: the FVP's P2-P5 skipped (barriers kept)
 #else
@@ -324,6 +372,8 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
     float* GPf = reinterpret_cast<float*>(sb + L::oGP);
     float* GPT = reinterpret_cast<float*>(sb + L::oGPT);
     float* G1T = reinterpret_cast<float*>(sb + L::oG1T);
+    float* OM = G1T;   // FVP: f32 [BT][LD] 1 - a0^2 (P1 -> P2), in the G1T region before P4 writes it
+    static_assert(BT * L::LD <= H * L::LDT, "OM in the G1T region");
     char* A0i = sb + L::oA0;
     char* A1i = sb + L::oA1;
 
@@ -337,6 +387,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, q = lane >> 4;
     const int cb = w & 3, kh = w >> 2;
+    float* bcs = reinterpret_cast<float*>(sb + L::oBC) + w * 16;   // this wave's broadcast scratch (bcast4)
     const int m = a.m;
     const int64_t T = a.T;
     const int64_t ntiles = (T + BT - 1) / BT;
@@ -485,7 +536,9 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 }
             return;
         }
-        const char* src = reinterpret_cast<const char*>(a.xs) + (ok ? (rb_ + row) * (4 * NP) : 0);
+        // the tile's uniform base (scalar; past the rows for a tile that does not exist,
+        // where nothing is loaded) plus the row's 32-bit offset
+        const char* src = reinterpret_cast<const char*>(a.xs) + rb_ * (4 * NP) + (ok ? (unsigned)(row * (4 * NP)) : 0u);
 #pragma unroll
         for (int u = 0; u < L::XPER; ++u)
             if (u >= u0 && u < u1)
@@ -621,7 +674,9 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
         // EVAL has no weight-gradient phase: the next tile's xhat loads go right
         // after the publish, before this tile's unconditional row-pass loads
         if (MODE == EVAL) xload(tile + gridDim.x, ltid);
-        float pa0[4], pa1[4];   // FVP: cached a0 / a1 at (rows kh*16 + 4q + rr, unit cb*16 + r)
+        // FVP: cached a0 / a1 at (rows kh*16 + 4q + rr, unit cb*16 + r); from the end of
+        // P1 on 1 - a0^2 (of the image's a0) and 1 - a1^2
+        float pa0[4], pa1[4];
         if (MODE == FVP) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
@@ -629,9 +684,11 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 // rows past T read row 0 of the tile instead of zero: finite values whose
                 // output-layer weights are masked to zero (gp), so they add nothing, and
                 // no select pulls the wait for these L2 loads to the top of P1
-                const int64_t gi = (row_base + (row < nrow ? row : 0)) * H + cb * 16 + lr16;
-                pa0[rr] = a.a0[gi];
-                pa1[rr] = a.a1[gi];
+                // (the tile's uniform base in scalar registers plus a 32-bit lane offset: no
+                // 64-bit VALU address arithmetic)
+                const unsigned gi = (unsigned)((row < nrow ? row : 0) * H + cb * 16 + lr16);
+                pa0[rr] = (a.a0 + row_base * H)[gi];
+                pa1[rr] = (a.a1 + row_base * H)[gi];
             }
         }
         __syncthreads();
@@ -703,8 +760,17 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) dst[(i * 16 + 4 * lq + rr) * L::LD + cb * 16 + lr16] = acc1[i][rr];
-            astore4(A0i, cb * 16 + lr16, kh * 16 + 4 * lq, pa0);
+            // 1 - a0^2 of this lane's pairs, once: to OM (the G1T region, free from the
+            // previous tile's P5 to this tile's P4) as f32 [row][LD] for P2, whose four
+            // waves of a row block each rebuilt all of it from the image, and kept in
+            // registers for P5, whose lanes own the same (rows, unit) as here.  pa1 is
+            // needed as 1 - a1^2 only (P2, P4) once it is in its image.
+            astore4_om(A0i, cb * 16 + lr16, kh * 16 + 4 * lq, pa0, pa0);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) OM[(kh * 16 + 4 * lq + rr) * L::LD + cb * 16 + lr16] = pa0[rr];
             astore4(A1i, cb * 16 + lr16, kh * 16 + 4 * lq, pa1);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) pa1[rr] = __builtin_fmaf(-pa1[rr], pa1[rr], 1.f);
             __syncthreads();
             KX_STAMP(1);
             KX_STAMP(2);
@@ -738,7 +804,8 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
             float rinv = 1.f;
             if (MODE == FVP) {
                 // d0 = (partial_kh0 + partial_kh1) (1 - a0^2), times the W1c column scale,
-                // scaled per row and split: d0 W1^T;  + a0 dW1^T (dW1r), a0 from the image
+                // scaled per row and split: d0 W1^T;  + a0 dW1^T (dW1r), a0 from the image,
+                // 1 - a0^2 from OM (P1)
                 half8 xh[2], xl[2], ah[2], al[2];
                 float8v dv[2];
                 float mx = 0.f;
@@ -746,14 +813,12 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 for (int s = 0; s < 2; ++s) {
                     arow(A0i, kh, s, lq, lr16, xh[s], xl[s]);
                     const int o = (kh * 16 + lr16) * L::LD + 32 * s + 8 * lq;
-                    const float8v av = hilo8(xh[s], xl[s]) * AHR_INV;
-                    dv[s] = (load8(D0 + o) + load8(D0B + o)) * (1.f - av * av);   // W1c column scale folded in P1
+                    dv[s] = (load8(D0 + o) + load8(D0B + o)) * load8(OM + o);   // W1c column scale folded in P1
                     mx = fmaxf(mx, absmax8(dv[s]));
                 }
                 const float sc = pow2_scale(max_over_groups(mx), rinv);
                 float ri[4];
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) ri[rr] = __shfl(rinv, 4 * lq + rr, 64);
+                bcast4(bcs, rinv, lq, lr16, ri);
                 floatx4 accb = zero4();
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
@@ -787,7 +852,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 const int row = kh * 16 + 4 * lq + rr;
                 const float v = acc[rr] + bias1;
                 if (MODE == FVP) {
-                    D1[row * L::LD + j] = (1.f - pa1[rr] * pa1[rr]) * v;
+                    D1[row * L::LD + j] = pa1[rr] * v;   // pa1: 1 - a1^2
                 } else {
                     av[rr] = tanhf(v);
                     if (MODE == FWD && row < nrow) a.a1[(row_base + row) * H + j] = av[rr];
@@ -806,8 +871,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 half8 ah[2], al[2];
                 const float rinv = adyn<2>(D1, L::LD, rb3, lq, lr16, sc3, ah, al);
                 float ri[4];
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) ri[rr] = __shfl(rinv, 4 * lq + rr, 64);
+                bcast4(bcs, rinv, lq, lr16, ri);
                 floatx4 accb = zero4();
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
@@ -884,8 +948,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
             half8 ah[1], al[1];
             const float rinv = adyn<1>(GPf, L::LDG, kh, lq, lr16, nullptr, ah, al);
             float ri[4];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) ri[rr] = __shfl(rinv, 4 * lq + rr, 64);
+            bcast4(bcs, rinv, lq, lr16, ri);
             half8 bh, bl;
             wcol(S3, L::WIMG2, cb, 0, lq, lr16, bh, bl);
             const floatx4 acc = mfma_x3(ah[0], al[0], bh, bl, zero4());
@@ -895,8 +958,8 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const int row = kh * 16 + 4 * lq + rr;
-                const float av = MODE == FVP ? pa1[rr] : a4[rr];
-                gv[rr] = (1.f - av * av) * (acc[rr] * ri[rr] * csc);
+                const float om = MODE == FVP ? pa1[rr] : 1.f - a4[rr] * a4[rr];   // FVP: pa1 is 1 - a1^2
+                gv[rr] = om * (acc[rr] * ri[rr] * csc);
                 D0[row * L::LD + hcol] = gv[rr];   // G1
             }
             *reinterpret_cast<float4*>(G1T + hcol * L::LDT + kh * 16 + 4 * lq) = make_float4(gv[0], gv[1], gv[2], gv[3]);
@@ -912,8 +975,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 float inv;
                 const float sc = pow2_scale(max_over_groups(absmax8(v)), inv);
                 split8(v, sc, gh, gl);
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) s4[rr] = __shfl(inv * AHR_INV, 4 * lq + rr, 64);
+                bcast4(bcs, inv * AHR_INV, lq, lr16, s4);
                 if ((w & 3) == 0) {
                     b2acc += sum_over_groups(((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])));
                 }
@@ -936,8 +998,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
             half8 ah[2], al[2];
             const float rinv = adyn<2>(D0, L::LD, kh, lq, lr16, nullptr, ah, al);
             float ri[4];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) ri[rr] = __shfl(rinv, 4 * lq + rr, 64);
+            bcast4(bcs, rinv, lq, lr16, ri);
             floatx4 acc = zero4();
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -947,12 +1008,18 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
             }
             const float csc = sc1[hcol];
             float gv[4], a4[4];
-            aval4(A0i, hcol, kh * 16 + 4 * lq, a4);
+            // FVP: this lane's 1 - a0^2 is still in its registers since P1 (the same rows and
+            // unit).  Not for <16, 12>, where the four live registers cost one spilled VGPR
+            // (a launch constant, but scratch all the same): it reads the image as FWD does.
+            // (1M-row Humanoid FVP: registers 847 us, image 847 - 853 us, before 870 us;
+            // profiles/r09a/README.md)
+            constexpr bool OMREG = MODE == FVP && KX_OM_REG && !(MP == 16 && KG == 12);
+            if (!OMREG) aval4(A0i, hcol, kh * 16 + 4 * lq, a4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const int row = kh * 16 + 4 * lq + rr;
-                const float av = a4[rr];
-                gv[rr] = (1.f - av * av) * (acc[rr] * ri[rr] * csc) * Us[row];
+                const float om = OMREG ? pa0[rr] : 1.f - a4[rr] * a4[rr];   // OMREG: pa0 is 1 - a0^2 (P1)
+                gv[rr] = om * (acc[rr] * ri[rr] * csc) * Us[row];
             }
             *reinterpret_cast<float4*>(D1 + hcol * L::LDT + kh * 16 + 4 * lq) = make_float4(gv[0], gv[1], gv[2], gv[3]);
         };
@@ -965,8 +1032,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
                 float inv;
                 const float sc = pow2_scale(max_over_groups(absmax8(v)), inv);
                 split8(v, sc, gh, gl);
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) s4[rr] = __shfl(inv * AHR_INV, 4 * lq + rr, 64);
+                bcast4(bcs, inv * AHR_INV, lq, lr16, s4);
                 if (kh == 0) {
                     b1acc += sum_over_groups(((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])));
                 }
@@ -999,7 +1065,7 @@ __global__ void __launch_bounds__(KT, 1) k_kx(RowArgs a, FOut o) {
             // gW0 (xhat transposed reads)
             half8 gh, gl;
             float s4[4];
-            gdyn(D1, L::LDT, cb, lq, lr16, gh, gl, s4);   // G0T
+            gdyn(D1, L::LDT, cb, lq, lr16, gh, gl, s4, bcs);   // G0T
             KX_STAMP(11);
 #pragma unroll
             for (int g = 0; g < KG; ++g) {
