@@ -600,6 +600,32 @@ int mjrl_policy_fit_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, 
                           const mjrl_policy_net* net, const mjrl_adam* hp, float* scratch, int32_t steps_per_launch,
                           float* grad_out, float* loss_out, void* stream);
 
+/* ---- MSE behaviour cloning's minibatch Adam steps on the policy's mean network
+ * (mjrl/algos/behavior_cloning_2.py:46-71) ----
+ * The six tensors of Linear(n, h0) - tanh - Linear(h0, h1) - tanh - Linear(h1, m) and their Adam
+ * state, device pointers in torch's parameter order W0, b0, W1, b1, W2, b2: the policy without
+ * its log_std, which this fit neither reads nor trains. */
+typedef struct mjrl_mean_net {
+    float* p[6];              /* the parameters */
+    float* exp_avg[6];        /* Adam's first moments, the parameters' shapes */
+    float* exp_avg_sq[6];     /* Adam's second moments */
+} mjrl_mean_net;
+/* mjrl_policy_fit_epoch's steps under the loss L = (1 / (bs m)) sum_ij (mean_ij - act_ij)^2
+ * (torch's MSELoss, mean reduction, over the minibatch's unmasked rows i and the m columns j; a
+ * masked row adds nothing and the divisor stays bs m).  Of data it reads obs, act, the four
+ * transformation vectors, T, n, m, h0 and h1; adv, ll_old, old_log_std, kind and clip are NOT
+ * read.  idx, bs, hp, scratch (mjrl_policy_fit_scratch floats), steps_per_launch, loss_out and
+ * stream as there; grad_out: null or [nmb][d6], d6 = h0 n + h0 + h1 h0 + h1 + m h1 + m.  The same
+ * kernel with the head fixed at compile time: the same fixed-order sums, no atomics, the same
+ * bits however the steps are split over calls and launches.  MJRL_EINVAL before any launch for
+ * a null data, n outside 1..2^24, m / h0 / h1 outside 1..64, bs outside 1..64, a negative T, nmb
+ * or steps_per_launch, and, when nmb > 0, a null idx, net, hp, scratch, obs, act or
+ * transformation vector, a negative step0 or a null pointer inside net; nmb == 0 is MJRL_OK
+ * without a launch. */
+int mjrl_policy_mse_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+                          const mjrl_mean_net* net, const mjrl_adam* hp, float* scratch, int32_t steps_per_launch,
+                          float* grad_out, float* loss_out, void* stream);
+
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----
  * dst[rows][n] = float(src) (round to nearest, as torch .float()), and when cmin /

@@ -112,7 +112,7 @@ def scratch(cached, query, dims, device):
 
 
 def fill_net(net, opt, params):
-    """net (_lib.ValueNet / PolicyNet): the parameters' and moments' device pointers."""
+    """net (_lib.ValueNet / PolicyNet / MeanNet): the parameters' and moments' device pointers."""
     for i, p in enumerate(params):
         st = opt.state[p]
         net.p[i], net.exp_avg[i], net.exp_avg_sq[i] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()

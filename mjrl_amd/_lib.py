@@ -56,6 +56,11 @@ class PolicyNet(C.Structure):
     _fields_ = [("p", C.c_void_p * 7), ("exp_avg", C.c_void_p * 7), ("exp_avg_sq", C.c_void_p * 7)]
 
 
+class MeanNet(C.Structure):
+    """mjrl_mean_net: the policy's mean network (no log_std) and its Adam moments, torch order."""
+    _fields_ = [("p", C.c_void_p * 6), ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6)]
+
+
 class PolicyFitData(C.Structure):
     """mjrl_policy_fit_data"""
     _fields_ = [(k, C.c_void_p) for k in ("obs", "act", "adv", "ll_old", "old_log_std", "in_shift", "in_scale",
@@ -150,6 +155,8 @@ SIGNATURES = {
     "mjrl_value_mlp_epoch": [P, P, I64, I32, P, I64, I32, C.POINTER(ValueNet), C.POINTER(Adam), P, P, P, P],
     "mjrl_policy_fit_scratch": [I32, I32, I32, I32, I32, C.POINTER(I64)],
     "mjrl_policy_fit_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(PolicyNet), C.POINTER(Adam), P, I32,
+                              P, P, P],
+    "mjrl_policy_mse_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(MeanNet), C.POINTER(Adam), P, I32,
                               P, P, P],
     "mjrl_build_flags": [],
     "mjrl_host_stage_f64": [P, I64, I32, P, P, P],

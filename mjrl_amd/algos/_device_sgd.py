@@ -20,6 +20,10 @@ fit_backend = "hip" on BC / PPO (opt-in) replaces the graph replays of an epoch 
 one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on the same device
 parameters and the device optimizer's moments: DeviceTrainer.fused_epoch, limits
 in check_fit_backend.
+
+MSE behaviour cloning (behavior_cloning_2.py) trains policy.model.parameters()
+alone: DeviceTrainer(..., params=...) mirrors that list instead of
+policy.trainable_params, and fused_epoch("mse", ...) is mjrl_policy_mse_epoch.
 """
 import numpy as np
 import torch
@@ -40,12 +44,15 @@ def default_device(device=None):
 
 
 class DeviceTrainer:
-    def __init__(self, policy, optimizer, device=None):
+    def __init__(self, policy, optimizer, device=None, params=None):
+        """params: the CPU tensors this trainer mirrors and trains, policy.trainable_params
+        unless given (behavior_cloning_2.py trains policy.model.parameters() alone)."""
         self.policy = policy
         self.cpu_opt = optimizer
         self.device = default_device(device)
+        self._cpu_params = None if params is None else list(params)
         self.params = [torch.zeros(p.shape, dtype=torch.float32, device=self.device, requires_grad=True)
-                       for p in policy.trainable_params]
+                       for p in self.cpu_params]
         self.graphable = self.device.type == "cuda" and "capturable" in optimizer.defaults
         kw = dict(optimizer.defaults)
         if self.graphable:
@@ -54,13 +61,17 @@ class DeviceTrainer:
         self._graphs = {}
         self._tf = None
 
+    @property
+    def cpu_params(self):
+        return self.policy.trainable_params if self._cpu_params is None else self._cpu_params
+
     # ---- CPU <-> device ------------------------------------------------------
     def pull(self):
         """policy params + optimizer state (CPU) -> device."""
         with torch.no_grad():
-            for d, c in zip(self.params, self.policy.trainable_params):
+            for d, c in zip(self.params, self.cpu_params):
                 d.copy_(c.data)
-        _fit.state_to_device(self.cpu_opt, self.policy.trainable_params, self.opt, self.params, self.device,
+        _fit.state_to_device(self.cpu_opt, self.cpu_params, self.opt, self.params, self.device,
                              self.graphable)
         for gd, gc in zip(self.opt.param_groups, self.cpu_opt.param_groups):
             for k, v in gc.items():
@@ -83,9 +94,9 @@ class DeviceTrainer:
         """device params + optimizer state -> the CPU policy / optimizer (the
         Parameter objects keep their identity: the CPU optimizer stays bound)."""
         with torch.no_grad():
-            for d, c in zip(self.params, self.policy.trainable_params):
+            for d, c in zip(self.params, self.cpu_params):
                 c.data.copy_(d.detach().cpu())
-        _fit.state_to_cpu(self.cpu_opt, self.policy.trainable_params, self.opt, self.params)
+        _fit.state_to_cpu(self.cpu_opt, self.cpu_params, self.opt, self.params)
 
     # ---- the policy on the device -----------------------------------------------
     def mean(self, obs, params=None):
@@ -153,7 +164,9 @@ class DeviceTrainer:
         the current stream: self.params and the device optimizer's exp_avg /
         exp_avg_sq are updated in place, then every step counter advances by nmb.
         kind: "bc" or "ppo"; obs / act / adv / ll_old: this call's f32 device rows;
-        old_log_std: PPO's aliased form (PPO._old_on_device) instead of ll_old."""
+        old_log_std: PPO's aliased form (PPO._old_on_device) instead of ll_old.
+        kind "mse": mjrl_policy_mse_epoch on a trainer over the six tensors of
+        policy.model.parameters() (behavior_cloning_2.py), obs / act alone."""
         from .. import _lib
         nmb, bs = int(idx_batches.shape[0]), int(idx_batches.shape[1])
         if nmb == 0:
@@ -168,7 +181,11 @@ class DeviceTrainer:
         K = _lib.calls()
         self._hip_scratch = _fit.scratch(getattr(self, "_hip_scratch", None), K.mjrl_policy_fit_scratch,
                                          (self.policy.n, self.policy.m, *self.policy.hidden, bs), dev)
-        net = _fit.fill_net(_lib.PolicyNet(), self.opt, self.params)
+        mse = kind == "mse"
+        if len(self.params) != (6 if mse else 7):
+            raise ValueError("the fused %s fit trains %s" % (kind, "policy.model.parameters()" if mse
+                                                             else "policy.trainable_params"))
+        net = _fit.fill_net(_lib.MeanNet() if mse else _lib.PolicyNet(), self.opt, self.params)
         ptr = lambda t: None if t is None else t.data_ptr()
         data = _lib.PolicyFitData(ptr(obs), ptr(act), ptr(adv), ptr(ll_old), ptr(old_log_std),
                                   *[t.data_ptr() for t in self._tf], int(obs.shape[0]), self.policy.n, self.policy.m,
@@ -176,17 +193,19 @@ class DeviceTrainer:
                                   _lib.POLICY_FIT_PPO if kind == "ppo" else _lib.POLICY_FIT_BC, float(clip))
         hp = _fit.adam_hp(self.opt, self.params)
         with torch.cuda.device(dev):
-            K.mjrl_policy_fit_epoch(data, idx_batches, nmb, bs, net, hp, self._hip_scratch, 0, None, None,
-                                    _lib.stream_ptr(torch.cuda.current_stream(dev)))
+            (K.mjrl_policy_mse_epoch if mse else K.mjrl_policy_fit_epoch)(
+                data, idx_batches, nmb, bs, net, hp, self._hip_scratch, 0, None, None,
+                _lib.stream_ptr(torch.cuda.current_stream(dev)))
         _fit.advance_steps(self.opt, self.params, nmb)
 
 
 HIP_MAX_WIDTH = 64    # the fused kernel's largest hidden / action width (csrc/policy_fit.hip)
 
 
-def check_fit_backend(who, backend, policy, optimizer, mb_size, device):
+def check_fit_backend(who, backend, policy, optimizer, mb_size, device, mean_only=False):
     """The fused route's limits, each a ValueError naming it, before anything
-    touches the GPU library.  Returns True when the backend is "hip"."""
+    touches the GPU library.  Returns True when the backend is "hip".
+    mean_only: the MSE fit's net, the optimizer over policy.model.parameters() alone."""
     if backend not in FIT_BACKENDS:
         raise ValueError("%s.fit_backend must be one of %s, not %r" % (who, FIT_BACKENDS, backend))
     if backend != "hip":
@@ -208,6 +227,11 @@ def check_fit_backend(who, backend, policy, optimizer, mb_size, device):
     g = optimizer.param_groups[0]
     if g.get("amsgrad", False) or g.get("maximize", False):
         raise ValueError("%s takes Adam with amsgrad=False and maximize=False" % pre)
+    if mean_only:
+        want, have = list(policy.model.parameters()), g["params"]
+        if len(have) != len(want) or any(a is not b for a, b in zip(have, want)):
+            raise ValueError("%s takes an Adam optimizer over exactly policy.model.parameters(), in their order "
+                             "(log_std is not trained), not over %d tensors" % (pre, len(have)))
     if default_device(device).type != "cuda":
         raise ValueError("%s runs on the GPU, not on the %s trainer device" % (pre, default_device(device)))
     return True

@@ -41,6 +41,12 @@
 // on the host in f64 from t alone.  Rows bs .. 63 and a row whose index is outside
 // [0, T) are masked: nothing of obs / act / adv / ll_old is read for them, their
 // dL/dLL is 0, the mean still divides by bs.
+//
+// k_pfit<true> is the same step under the MSE head of mjrl/algos/behavior_cloning_2.py:46-50
+// (mjrl_policy_mse_epoch): L = sum (mu - act)^2 / (bs m) over the unmasked rows, on the six
+// tensors of the mean network.  Phase 1 takes sigma = 1 and never reads log_std, phase 4's
+// z is act - mu, phase 5's row term is sum z^2 / m with -2 / (bs m) in dL/dLL's place,
+// phases 6 and 9 have no log_std.  p[6] / m[6] / v[6] are null there and nothing touches them.
 #include "fit.h"
 
 using namespace mjrl;
@@ -98,6 +104,9 @@ struct PfitArgs {
     float step_size[PF_SPL], bc2s[PF_SPL];   // hp's other two fields for each step of this launch
 };
 
+// MSE: the mean-squared-error head (behavior_cloning_2.py:46-50) on the six tensors of the mean
+// network, a compile-time switch so that the BC / PPO instantiation stays the code it was.
+template <bool MSE>
 __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
     __shared__ __attribute__((aligned(16))) float Xs[PR * XLD];    // xhat, one chunk of columns
     __shared__ __attribute__((aligned(16))) float a0s[PR * PLD];
@@ -227,6 +236,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
                 i = i >= 0 && i < a.T ? i : -1;
             }
             s_row[lane] = i;
+        } else if (MSE) {
+            if (w == 1) s_gsc[lane] = lane < m ? a.out_scale[lane] : 0.f;   // sigma is 1: log_std is not read
         } else if (w == 1) {
             const float lsv = lane < m ? ls[lane] : 0.f;
             const float sg = expf(lsv);
@@ -322,7 +333,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
             const int col = 16 * ub + r;
             const bool in = col < m;
             const float bias = in ? b2[col] : 0.f, osc = in ? a.out_scale[col] : 0.f, osh = in ? a.out_shift[col] : 0.f;
-            const float sg = s_sig[col];
+            const float sg = MSE ? 1.f : s_sig[col];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -332,7 +343,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
                     float z = 0.f;
                     if (in && xi >= 0) {   // nothing of act is read for a masked row
                         const float mu = (acc[i][k] + bias) * osc + osh;
-                        z = (a.act[xi * m + col] - mu) / sg;
+                        z = a.act[xi * m + col] - mu;
+                        if (!MSE) z = z / sg;
                     }
                     zs[row * PLD + col] = z;
                 }
@@ -350,20 +362,27 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
                 if (col < m) {
                     const double z = (double)zs[row * PLD + col];
                     sz += z * z;
-                    sd += z * z * s_q[col];
+                    if (!MSE) sd += z * z * s_q[col];
                 }
             }
             sz += __shfl_xor(sz, 1, 64);
-            sd += __shfl_xor(sd, 1, 64);
+            if (!MSE) sd += __shfl_xor(sd, 1, 64);
             sz += __shfl_xor(sz, 2, 64);
-            sd += __shfl_xor(sd, 2, 64);
+            if (!MSE) sd += __shfl_xor(sd, 2, 64);
             sz += __shfl_xor(sz, 4, 64);
-            sd += __shfl_xor(sd, 4, 64);
+            if (!MSE) sd += __shfl_xor(sd, 4, 64);
             if (part == 0) {
                 const int64_t xi = s_row[row];
                 float gll = 0.f;
                 double lrow = 0.0;
-                if (xi >= 0) {
+                if (MSE) {
+                    // the row's term is sum z^2 / m, z = act - mu; -2 / (bs m) in gll's place makes
+                    // gmu below 2 (mu - act) out_scale / (bs m)
+                    if (xi >= 0) {
+                        gll = -2.f / (float)(bs * m);
+                        lrow = sz / (double)m;
+                    }
+                } else if (xi >= 0) {
                     const double LL = -0.5 * sz - s_lsum[0] - (double)m * HALF_LOG_2PI;
                     if (a.kind == PF_BC) {
                         gll = -1.f / (float)bs;
@@ -389,7 +408,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
 
         // ---- 6: d log_std (wave 0), the step's loss (wave 1); then gmu in place of z ----
         float dls = 0.f;
-        if (w == 0) {
+        if (!MSE && w == 0) {
             if (lane < m) {
                 double s = 0.0;
                 for (int row = 0; row < PR; ++row) {
@@ -465,7 +484,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
         PF_STAMP(8);
 
         // ---- 9: the weight gradients and Adam; every read of this step's parameters is behind us ----
-        if (w == 0 && lane < m) {
+        if (!MSE && w == 0 && lane < m) {
             float p1, m1, v1;
             adam_step(ls[lane], a.m[6][lane], a.v[6][lane], dls, hp, p1, m1, v1);
             if (grad) grad[o_ls + lane] = dls;
@@ -511,6 +530,64 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
 #endif
 }
 
+// What both entry points share once their arguments are checked: the sizes, the row and
+// transformation pointers, the 16-byte-load flags, then the launches of nmb steps, at most
+// PF_SPL a launch.  a.p / m / v, a.adv / ll_old / old_ls, a.kind and the clip range are the caller's.
+template <bool MSE>
+int run_steps(PfitArgs& a, const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+              const mjrl_adam* hp, float* scratch, int32_t steps_per_launch, float* grad_out, float* loss_out,
+              void* stream) {
+    const int n = data->n, m = data->m, h0 = data->h0, h1 = data->h1;
+    hipStream_t st = (hipStream_t)stream;
+    const int spl = steps_per_launch == 0 || steps_per_launch > PF_SPL ? PF_SPL : steps_per_launch;
+    a.obs = data->obs;
+    a.act = data->act;
+    a.in_shift = data->in_shift;
+    a.in_scale = data->in_scale;
+    a.out_shift = data->out_shift;
+    a.out_scale = data->out_scale;
+    a.T = data->T;
+    a.scratch = scratch;
+    a.scap = PF_SCRATCH;
+    a.d = (int64_t)h0 * n + h0 + (int64_t)h1 * h0 + h1 + (int64_t)m * h1 + m + (MSE ? 0 : m);
+    a.n = n;
+    a.na = m;
+    a.h0 = h0;
+    a.h1 = h1;
+    a.bs = bs;
+    const auto al16 = [](const void* p) { return (uintptr_t)p % 16 == 0; };
+    a.vx = n % 4 == 0 && al16(data->obs) && al16(data->in_shift) && al16(data->in_scale);
+    a.vw0 = n % 4 == 0 && al16(a.p[0]);
+    a.vw1 = h0 % 4 == 0 && al16(a.p[2]);
+    a.vw2 = h1 % 4 == 0 && al16(a.p[4]);
+    a.hp = adam_consts(hp);
+    for (int64_t k0 = 0; k0 < nmb; k0 += spl) {
+        const int ns = (int)(nmb - k0 < spl ? nmb - k0 : spl);
+        for (int s = 0; s < ns; ++s) adam_bias(hp, k0 + s, a.step_size[s], a.bc2s[s]);
+        for (int s = ns; s < PF_SPL; ++s) a.step_size[s] = a.bc2s[s] = 1.f;
+        a.nsteps = ns;
+        a.idx = idx + k0 * bs;
+        a.grad = grad_out ? grad_out + k0 * a.d : nullptr;
+        a.loss = loss_out ? loss_out + k0 : nullptr;
+        hipLaunchKernelGGL(k_pfit<MSE>, dim3(1), dim3(PF_THREADS), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
+// the checks both entry points make on what they both read; nmb > 0: the pointers too
+bool sizes_ok(const mjrl_policy_fit_data* data, int64_t nmb, int32_t bs, int32_t steps_per_launch) {
+    if (!data || bs < 1 || bs > PR || nmb < 0 || steps_per_launch < 0) return false;
+    const int n = data->n, m = data->m, h0 = data->h0, h1 = data->h1;
+    // n <= 2^24: the kernel indexes a tensor's elements with 32 bits
+    return n > 0 && n <= (1 << 24) && m >= 1 && m <= PH && h0 >= 1 && h0 <= PH && h1 >= 1 && h1 <= PH && data->T >= 0;
+}
+
+bool pointers_ok(const mjrl_policy_fit_data* data, const int64_t* idx, const void* net, const mjrl_adam* hp,
+                 const float* scratch) {
+    if (!idx || !net || !hp || !scratch || hp->step0 < 0) return false;
+    return data->obs && data->act && data->in_shift && data->in_scale && data->out_shift && data->out_scale;
+}
+
 }  // namespace
 
 extern "C" {
@@ -525,60 +602,42 @@ int mjrl_policy_fit_scratch(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_
 int mjrl_policy_fit_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
                           const mjrl_policy_net* net, const mjrl_adam* hp, float* scratch, int32_t steps_per_launch,
                           float* grad_out, float* loss_out, void* stream) {
-    if (!data || bs < 1 || bs > PR || nmb < 0 || steps_per_launch < 0) return MJRL_EINVAL;
-    const int n = data->n, m = data->m, h0 = data->h0, h1 = data->h1;
-    // n <= 2^24: the kernel indexes a tensor's elements with 32 bits
-    if (n <= 0 || n > (1 << 24) || m < 1 || m > PH || h0 < 1 || h0 > PH || h1 < 1 || h1 > PH || data->T < 0)
-        return MJRL_EINVAL;
+    if (!sizes_ok(data, nmb, bs, steps_per_launch)) return MJRL_EINVAL;
     if (data->kind != MJRL_POLICY_FIT_BC && data->kind != MJRL_POLICY_FIT_PPO) return MJRL_EINVAL;
     if (data->kind == MJRL_POLICY_FIT_PPO && (!data->ll_old == !data->old_log_std)) return MJRL_EINVAL;
     if (nmb == 0) return MJRL_OK;
-    if (!idx || !net || !hp || !scratch || hp->step0 < 0) return MJRL_EINVAL;
-    if (!data->obs || !data->act || !data->in_shift || !data->in_scale || !data->out_shift || !data->out_scale)
-        return MJRL_EINVAL;
+    if (!pointers_ok(data, idx, net, hp, scratch)) return MJRL_EINVAL;
     if (data->kind == MJRL_POLICY_FIT_PPO && !data->adv) return MJRL_EINVAL;
     PfitArgs a;
     if (!net_ptrs(net, a.p, a.m, a.v)) return MJRL_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int spl = steps_per_launch == 0 || steps_per_launch > PF_SPL ? PF_SPL : steps_per_launch;
-    a.obs = data->obs;
-    a.act = data->act;
     a.adv = data->adv;
     a.ll_old = data->kind == MJRL_POLICY_FIT_PPO ? data->ll_old : nullptr;
     a.old_ls = data->kind == MJRL_POLICY_FIT_PPO ? data->old_log_std : nullptr;
-    a.in_shift = data->in_shift;
-    a.in_scale = data->in_scale;
-    a.out_shift = data->out_shift;
-    a.out_scale = data->out_scale;
-    a.T = data->T;
-    a.scratch = scratch;
-    a.scap = PF_SCRATCH;
-    a.d = (int64_t)h0 * n + h0 + (int64_t)h1 * h0 + h1 + (int64_t)m * h1 + m + m;
-    a.n = n;
-    a.na = m;
-    a.h0 = h0;
-    a.h1 = h1;
-    a.bs = bs;
     a.kind = data->kind == MJRL_POLICY_FIT_PPO ? PF_PPO : PF_BC;
-    const auto al16 = [](const void* p) { return (uintptr_t)p % 16 == 0; };
-    a.vx = n % 4 == 0 && al16(data->obs) && al16(data->in_shift) && al16(data->in_scale);
-    a.vw0 = n % 4 == 0 && al16(net->p[0]);
-    a.vw1 = h0 % 4 == 0 && al16(net->p[2]);
-    a.vw2 = h1 % 4 == 0 && al16(net->p[4]);
     a.clip_lo = (float)(1.0 - data->clip);
     a.clip_hi = (float)(1.0 + data->clip);
-    a.hp = adam_consts(hp);
-    for (int64_t k0 = 0; k0 < nmb; k0 += spl) {
-        const int ns = (int)(nmb - k0 < spl ? nmb - k0 : spl);
-        for (int s = 0; s < ns; ++s) adam_bias(hp, k0 + s, a.step_size[s], a.bc2s[s]);
-        for (int s = ns; s < PF_SPL; ++s) a.step_size[s] = a.bc2s[s] = 1.f;
-        a.nsteps = ns;
-        a.idx = idx + k0 * bs;
-        a.grad = grad_out ? grad_out + k0 * a.d : nullptr;
-        a.loss = loss_out ? loss_out + k0 : nullptr;
-        hipLaunchKernelGGL(k_pfit, dim3(1), dim3(PF_THREADS), 0, st, a);
+    return run_steps<false>(a, data, idx, nmb, bs, hp, scratch, steps_per_launch, grad_out, loss_out, stream);
+}
+
+int mjrl_policy_mse_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+                          const mjrl_mean_net* net, const mjrl_adam* hp, float* scratch, int32_t steps_per_launch,
+                          float* grad_out, float* loss_out, void* stream) {
+    if (!sizes_ok(data, nmb, bs, steps_per_launch)) return MJRL_EINVAL;
+    if (nmb == 0) return MJRL_OK;
+    if (!pointers_ok(data, idx, net, hp, scratch)) return MJRL_EINVAL;
+    PfitArgs a;
+    float *p6[6], *m6[6], *v6[6];
+    if (!net_ptrs(net, p6, m6, v6)) return MJRL_EINVAL;
+    for (int i = 0; i < 6; ++i) {
+        a.p[i] = p6[i];
+        a.m[i] = m6[i];
+        a.v[i] = v6[i];
     }
-    return (int)hipGetLastError();
+    a.p[6] = a.m[6] = a.v[6] = nullptr;   // no log_std in this net: the MSE instantiation never touches them
+    a.adv = a.ll_old = a.old_ls = nullptr;   // data's adv / ll_old / old_log_std / kind / clip are not read
+    a.kind = PF_BC;
+    a.clip_lo = a.clip_hi = 1.f;
+    return run_steps<true>(a, data, idx, nmb, bs, hp, scratch, steps_per_launch, grad_out, loss_out, stream);
 }
 
 }  // extern "C"

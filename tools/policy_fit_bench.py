@@ -7,6 +7,11 @@ of torch ops per minibatch step) against "hip" (csrc/policy_fit.hip), at two sha
               (3,124 steps a call)
 
     python tools/policy_fit_bench.py [--alternations 3] [--timeout 300] [--shapes swimmer,humanoid]
+                                     [--algo ppo|bc_mse]
+
+--algo bc_mse times behavior_cloning_2.BC.train() (the MSE head, mjrl_policy_mse_epoch)
+instead, on synthetic expert paths of the same sizes: class defaults at swimmer (5
+epochs: 975 steps a call), epochs = 2 at humanoid (3,124 steps).
 
 The backends alternate: a warm-up pair whose times are dropped, then
 `--alternations` pairs.  Every run is a child process of its own under its own
@@ -43,7 +48,15 @@ def child(args):
     from mjrl_amd.utils.gym_env import EnvSpec
     n, m, npaths, H, kw = SHAPES[args.shape]
     policy = MLP(EnvSpec(n, m, H, 1), hidden_sizes=(64, 64), seed=1, init_log_std=-0.5)
-    agent = PPO(None, policy, None, **kw)
+    mse = args.algo == "bc_mse"
+    if mse:
+        from mjrl_amd.algos.behavior_cloning_2 import BC
+        # the constructor reads its paths for the transformations; every timed call gets its own
+        rs = np.random.RandomState(9)
+        agent = BC([dict(observations=rs.randn(H, n), actions=0.6 * rs.randn(H, m)) for _ in range(npaths)],
+                   policy, **kw)
+    else:
+        agent = PPO(None, policy, None, **kw)
     agent.fit_backend = args.child
     spent = [0.0]
 
@@ -67,7 +80,11 @@ def child(args):
         spent[0] = 0.0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        agent.train_from_paths(paths)
+        if mse:
+            agent.expert_paths = paths
+            agent.train()
+        else:
+            agent.train_from_paths(paths)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
         epochs_s.append(spent[0])
@@ -83,18 +100,22 @@ def main():
     ap.add_argument("--alternations", type=int, default=3)
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds per run (one child process)")
     ap.add_argument("--shapes", default="swimmer,humanoid")
+    ap.add_argument("--algo", choices=("ppo", "bc_mse"), default="ppo")
     ap.add_argument("--shape", default="swimmer", help=argparse.SUPPRESS)
     ap.add_argument("--child", choices=("torch", "hip"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(args)
     res = dict(tool="policy_fit_bench", shapes={})
+    if args.algo != "ppo":
+        res["algo"] = args.algo
     for shape in args.shapes.split(","):
         runs = {"torch": [], "hip": []}
         steps, norm = 0, {}
         for pair in range(args.alternations + 1):
             for backend in ("torch", "hip"):
-                cmd = [sys.executable, os.path.abspath(__file__), "--child", backend, "--shape", shape]
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", backend, "--shape", shape,
+                       "--algo", args.algo]
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
                 except subprocess.TimeoutExpired:
