@@ -570,7 +570,8 @@ typedef struct mjrl_policy_fit_data {
     const float *obs, *act, *adv, *ll_old, *old_log_std;
     const float *in_shift, *in_scale, *out_shift, *out_scale;
     int64_t T;
-    int32_t n, m, h0, h1;     /* 1 <= m, h0, h1 <= 64 */
+    int32_t n, m, h0, h1;     /* 1 <= m <= 64; 1 <= h0, h1 <= 64 for mjrl_policy_fit_epoch / mjrl_policy_mse_epoch,
+                               * <= 256 for mjrl_policy_fit_wide_epoch / mjrl_policy_mse_wide_epoch */
     int32_t kind;             /* MJRL_POLICY_FIT_BC / _PPO */
     double clip;              /* PPO's clip coefficient */
 } mjrl_policy_fit_data;
@@ -625,6 +626,30 @@ typedef struct mjrl_mean_net {
 int mjrl_policy_mse_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
                           const mjrl_mean_net* net, const mjrl_adam* hp, float* scratch, int32_t steps_per_launch,
                           float* grad_out, float* loss_out, void* stream);
+
+/* ---- the same steps for hidden layers up to 256 units wide (csrc/policy_fit_wide.hip) ----
+ * mjrl_policy_fit_epoch / mjrl_policy_mse_epoch with 1 <= h0, h1 <= 256 (1 <= m, bs <= 64 as
+ * there): the same structures, the same step, the same meaning of idx, net, hp, grad_out
+ * [nmb][d] and loss_out [nmb].  A step is three launches of its own (one workgroup per 16
+ * units of layer 0, one per 16 units of layer 1, one for the head), so there is no
+ * steps_per_launch; every dependency between workgroups is a kernel boundary, no launch waits
+ * on another workgroup, and every launch is bounded work of one step.  The tiles that cross
+ * a boundary live in the scratch: mjrl_policy_fit_wide_scratch floats (MJRL_EINVAL for n <= 0,
+ * m / bs outside 1..64, h0 / h1 outside 1..256 or a null result), 16-byte aligned, of which
+ * nothing but float [4 * 64 * 256], the last step's loss, means anything after a call.
+ * Exact-f32 MFMA, every sum in one fixed order, no atomics: the same state and arguments give
+ * the same bits, however nmb steps are split over calls (step0 advanced).  The sums are
+ * ordered as these kernels order them, so the bits are not mjrl_policy_fit_epoch's at the
+ * widths both take.  Never allocates, never synchronises.  MJRL_EINVAL before any launch for
+ * what mjrl_policy_fit_epoch / mjrl_policy_mse_epoch refuse, with these width limits;
+ * nmb == 0 is MJRL_OK without a launch. */
+int mjrl_policy_fit_wide_scratch(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int64_t* floats);
+int mjrl_policy_fit_wide_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+                               const mjrl_policy_net* net, const mjrl_adam* hp, float* scratch, float* grad_out,
+                               float* loss_out, void* stream);
+int mjrl_policy_mse_wide_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+                               const mjrl_mean_net* net, const mjrl_adam* hp, float* scratch, float* grad_out,
+                               float* loss_out, void* stream);
 
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----

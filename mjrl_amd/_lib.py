@@ -158,6 +158,11 @@ SIGNATURES = {
                               P, P, P],
     "mjrl_policy_mse_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(MeanNet), C.POINTER(Adam), P, I32,
                               P, P, P],
+    "mjrl_policy_fit_wide_scratch": [I32, I32, I32, I32, I32, C.POINTER(I64)],
+    "mjrl_policy_fit_wide_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(PolicyNet), C.POINTER(Adam), P,
+                                   P, P, P],
+    "mjrl_policy_mse_wide_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(MeanNet), C.POINTER(Adam), P,
+                                   P, P, P],
     "mjrl_build_flags": [],
     "mjrl_host_stage_f64": [P, I64, I32, P, P, P],
     "mjrl_host_stage_f32": [P, I64, I32, P, P, P],

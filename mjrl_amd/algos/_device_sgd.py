@@ -19,7 +19,9 @@ copy.  Optimizers without a capturable mode run the same step eagerly.
 fit_backend = "hip" on BC / PPO (opt-in) replaces the graph replays of an epoch by
 one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on the same device
 parameters and the device optimizer's moments: DeviceTrainer.fused_epoch, limits
-in check_fit_backend.
+in check_fit_backend.  fit_backend = "hip_wide" (opt-in too) is the
+same step sliced over workgroups for hidden layers up to 256 units wide
+(csrc/policy_fit_wide.hip, mjrl_policy_fit_wide_epoch): fused_epoch(..., wide=True).
 
 MSE behaviour cloning (behavior_cloning_2.py) trains policy.model.parameters()
 alone: DeviceTrainer(..., params=...) mirrors that list instead of
@@ -30,7 +32,10 @@ import torch
 import torch.nn.functional as F
 
 from .. import _device_fit as _fit
-from .._device_fit import FIT_BACKENDS, HIP_MAX_BATCH
+from .._device_fit import HIP_MAX_BATCH
+
+# PPO's, BC's and behavior_cloning_2.BC's fit_backend (MLPBaseline keeps _device_fit.FIT_BACKENDS)
+POLICY_FIT_BACKENDS = ("torch", "hip", "hip_wide")
 
 LOG_2PI = float(np.log(2 * np.pi))
 
@@ -159,14 +164,18 @@ class DeviceTrainer:
         return self._graphs[gkey]
 
     # ---- the fused route (fit_backend = "hip") -------------------------------------------
-    def fused_epoch(self, kind, obs, act, idx_batches, adv=None, ll_old=None, old_log_std=None, clip=0.0):
+    def fused_epoch(self, kind, obs, act, idx_batches, adv=None, ll_old=None, old_log_std=None, clip=0.0,
+                    wide=False):
         """epoch()'s steps as one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on
         the current stream: self.params and the device optimizer's exp_avg /
         exp_avg_sq are updated in place, then every step counter advances by nmb.
         kind: "bc" or "ppo"; obs / act / adv / ll_old: this call's f32 device rows;
         old_log_std: PPO's aliased form (PPO._old_on_device) instead of ll_old.
         kind "mse": mjrl_policy_mse_epoch on a trainer over the six tensors of
-        policy.model.parameters() (behavior_cloning_2.py), obs / act alone."""
+        policy.model.parameters() (behavior_cloning_2.py), obs / act alone.
+        wide: the sliced kernels of csrc/policy_fit_wide.hip (hidden layers up to 256
+        units; mjrl_policy_fit_wide_epoch / mjrl_policy_mse_wide_epoch) on the same
+        parameters and moments, with a scratch of their own."""
         from .. import _lib
         nmb, bs = int(idx_batches.shape[0]), int(idx_batches.shape[1])
         if nmb == 0:
@@ -179,8 +188,11 @@ class DeviceTrainer:
             raise ValueError("the fused policy fit takes contiguous f32 rows obs [T][n], act [T][m] on the trainer's device")
         idx_batches = idx_batches.contiguous()
         K = _lib.calls()
-        self._hip_scratch = _fit.scratch(getattr(self, "_hip_scratch", None), K.mjrl_policy_fit_scratch,
-                                         (self.policy.n, self.policy.m, *self.policy.hidden, bs), dev)
+        skey = "_hip_wide_scratch" if wide else "_hip_scratch"
+        scratch = _fit.scratch(getattr(self, skey, None),
+                               K.mjrl_policy_fit_wide_scratch if wide else K.mjrl_policy_fit_scratch,
+                               (self.policy.n, self.policy.m, *self.policy.hidden, bs), dev)
+        setattr(self, skey, scratch)
         mse = kind == "mse"
         if len(self.params) != (6 if mse else 7):
             raise ValueError("the fused %s fit trains %s" % (kind, "policy.model.parameters()" if mse
@@ -193,32 +205,42 @@ class DeviceTrainer:
                                   _lib.POLICY_FIT_PPO if kind == "ppo" else _lib.POLICY_FIT_BC, float(clip))
         hp = _fit.adam_hp(self.opt, self.params)
         with torch.cuda.device(dev):
-            (K.mjrl_policy_mse_epoch if mse else K.mjrl_policy_fit_epoch)(
-                data, idx_batches, nmb, bs, net, hp, self._hip_scratch, 0, None, None,
-                _lib.stream_ptr(torch.cuda.current_stream(dev)))
+            stream = _lib.stream_ptr(torch.cuda.current_stream(dev))
+            if wide:
+                (K.mjrl_policy_mse_wide_epoch if mse else K.mjrl_policy_fit_wide_epoch)(
+                    data, idx_batches, nmb, bs, net, hp, scratch, None, None, stream)
+            else:
+                (K.mjrl_policy_mse_epoch if mse else K.mjrl_policy_fit_epoch)(
+                    data, idx_batches, nmb, bs, net, hp, scratch, 0, None, None, stream)
         _fit.advance_steps(self.opt, self.params, nmb)
 
 
 HIP_MAX_WIDTH = 64    # the fused kernel's largest hidden / action width (csrc/policy_fit.hip)
+HIP_WIDE_MAX_WIDTH = 256   # the sliced kernels' largest hidden width (csrc/policy_fit_wide.hip); actions stay at 64
 
 
 def check_fit_backend(who, backend, policy, optimizer, mb_size, device, mean_only=False):
     """The fused route's limits, each a ValueError naming it, before anything
-    touches the GPU library.  Returns True when the backend is "hip".
+    touches the GPU library.  Returns True when the backend is "hip" or "hip_wide"
+    (the same checks, hidden widths 1..256).
     mean_only: the MSE fit's net, the optimizer over policy.model.parameters() alone."""
-    if backend not in FIT_BACKENDS:
-        raise ValueError("%s.fit_backend must be one of %s, not %r" % (who, FIT_BACKENDS, backend))
-    if backend != "hip":
+    if backend not in POLICY_FIT_BACKENDS:
+        raise ValueError("%s.fit_backend must be one of %s, not %r" % (who, POLICY_FIT_BACKENDS, backend))
+    if backend == "torch":
         return False
-    pre = '%s.fit_backend = "hip"' % who
+    pre = '%s.fit_backend = "%s"' % (who, backend)
+    max_h = HIP_WIDE_MAX_WIDTH if backend == "hip_wide" else HIP_MAX_WIDTH
     if not 1 <= int(mb_size) <= HIP_MAX_BATCH:
         raise ValueError("%s takes minibatches of 1..%d rows, not %d" % (pre, HIP_MAX_BATCH, mb_size))
     hidden = policy.hidden
     if hidden is None:
         raise ValueError("%s trains the Gaussian MLP policy (two hidden layers), not a LinearPolicy" % pre)
-    if len(hidden) != 2 or not all(1 <= int(h) <= HIP_MAX_WIDTH for h in hidden) or not 1 <= policy.m <= HIP_MAX_WIDTH:
-        raise ValueError("%s takes two hidden layers and an action width of 1..%d units each, not %r / %d"
-                         % (pre, HIP_MAX_WIDTH, tuple(hidden), policy.m))
+    if len(hidden) != 2 or not all(1 <= int(h) <= max_h for h in hidden) or not 1 <= policy.m <= HIP_MAX_WIDTH:
+        if max_h == HIP_MAX_WIDTH:
+            raise ValueError("%s takes two hidden layers and an action width of 1..%d units each, not %r / %d"
+                             % (pre, HIP_MAX_WIDTH, tuple(hidden), policy.m))
+        raise ValueError("%s takes two hidden layers of 1..%d units each and an action width of 1..%d, not %r / %d"
+                         % (pre, max_h, HIP_MAX_WIDTH, tuple(hidden), policy.m))
     if type(optimizer) is not torch.optim.Adam:
         raise ValueError("%s takes a torch.optim.Adam optimizer, not %s" % (pre, type(optimizer).__name__))
     if len(optimizer.param_groups) != 1:

@@ -13,7 +13,8 @@ set_param_values(params, set_new=True, set_old=True) (the log_std clamp).
 The expert rows are staged to the device once per train() call.
 fit_backend = "hip" (opt-in, per instance or on the class) runs the minibatch
 steps as the fused kernel of csrc/policy_fit.hip instead (batch_size <= 64, MLP
-policies up to 64 units wide).
+policies up to 64 units wide); fit_backend = "hip_wide" as the sliced
+kernels of csrc/policy_fit_wide.hip (hidden layers up to 256 units).
 """
 import logging
 import time as timer
@@ -29,7 +30,8 @@ logging.disable(logging.CRITICAL)
 
 class BC:
     # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
-    # csrc/policy_fit.hip (opt-in, per instance or on the class)
+    # csrc/policy_fit.hip (opt-in, per instance or on the class); "hip_wide": the sliced
+    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too)
     fit_backend = "torch"
 
     def __init__(self, expert_paths, policy, epochs=5, batch_size=64, lr=1e-3, optimizer=None, device=None):
@@ -98,7 +100,7 @@ class BC:
             self.logger.log_kv("time", timer.time() - ts)
             batches = choice_batches(num_samples, self.mb_size, tr.device)
             if hip:
-                tr.fused_epoch("bc", O, A, batches)
+                tr.fused_epoch("bc", O, A, batches, wide=self.fit_backend == "hip_wide")
             else:
                 tr.epoch(("bc", self._ncall), mb_loss, batches)
         tr.push()

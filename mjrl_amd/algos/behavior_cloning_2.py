@@ -17,7 +17,9 @@ The expert rows are staged to the device once per train() call.
 fit_backend = "hip" (opt-in, per instance or on the class) runs the minibatch
 steps as the fused kernel's MSE head (csrc/policy_fit.hip, mjrl_policy_mse_epoch;
 batch_size <= 64, MLP policies up to 64 units wide, Adam over exactly
-policy.model.parameters()).
+policy.model.parameters()); fit_backend = "hip_wide" as the sliced
+kernels of csrc/policy_fit_wide.hip (mjrl_policy_mse_wide_epoch; hidden layers up to
+256 units).
 """
 import logging
 import time as timer
@@ -33,7 +35,8 @@ logging.disable(logging.CRITICAL)
 
 class BC:
     # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
-    # csrc/policy_fit.hip (opt-in, per instance or on the class)
+    # csrc/policy_fit.hip (opt-in, per instance or on the class); "hip_wide": the sliced
+    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too)
     fit_backend = "torch"
 
     def __init__(self, expert_paths, policy, epochs=5, batch_size=64, lr=1e-3, optimizer=None, device=None):
@@ -109,7 +112,7 @@ class BC:
             self.logger.log_kv("time", timer.time() - ts)
             batches = choice_batches(num_samples, self.mb_size, tr.device)
             if hip:
-                tr.fused_epoch("mse", O, A, batches)
+                tr.fused_epoch("mse", O, A, batches, wide=self.fit_backend == "hip_wide")
             else:
                 tr.epoch(("bc_mse", self._ncall), mb_loss, batches)
         tr.push()

@@ -16,7 +16,9 @@ from the HIP engine's forward / evaluation passes (CPI_surrogate, kl_old_new).
 train_step is BatchREINFORCE's (device GAE), handing the paths with their
 advantages to train_from_paths.  fit_backend = "hip" (opt-in, per instance or on
 the class) runs the minibatch steps as the fused kernel of csrc/policy_fit.hip
-instead (mb_size <= 64, MLP policies up to 64 units wide).  Single process: the minibatch order is global,
+instead (mb_size <= 64, MLP policies up to 64 units wide), fit_backend =
+"hip_wide" as the sliced kernels of csrc/policy_fit_wide.hip (hidden layers up to 256
+units).  Single process: the minibatch order is global,
 so a sharded PPO is not offered (comm must be local).
 """
 import time as timer
@@ -32,7 +34,8 @@ from ..utils.logger import DataLog
 class PPO(BatchREINFORCE):
     _poolable = False   # the minibatch order is global: one process, even with MJRL_AMD_DEVICES set
     # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
-    # csrc/policy_fit.hip (opt-in, per instance or on the class)
+    # csrc/policy_fit.hip (opt-in, per instance or on the class); "hip_wide": the sliced
+    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too)
     fit_backend = "torch"
 
     def __init__(self, env, policy, baseline, clip_coef=0.2, epochs=10, mb_size=64, learn_rate=3e-4, seed=0,
@@ -91,9 +94,9 @@ class PPO(BatchREINFORCE):
     def _check_backend(self):
         hip = check_fit_backend("PPO", self.fit_backend, self.policy, self.optimizer, self.mb_size, self._device)
         if hip and self._aliasing() not in ([False] * 7, [True] * 6 + [False]):
-            raise ValueError('PPO.fit_backend = "hip" takes old parameters that share no storage with the new ones, '
+            raise ValueError('PPO.fit_backend = "%s" takes old parameters that share no storage with the new ones, '
                              "or the six mean-network tensors shared and log_std not (what set_param_values "
-                             "leaves), not %r" % (self._aliasing(),))
+                             "leaves), not %r" % (self.fit_backend, self._aliasing()))
         return hip
 
     def train_from_paths(self, paths):
@@ -148,7 +151,8 @@ class PPO(BatchREINFORCE):
             batches = choice_batches(num_samples, self.mb_size, dev)
             if hip:
                 tr.fused_epoch("ppo", O, A, batches, adv=ADV, ll_old=None if aliased else LL_old,
-                               old_log_std=old_dev[-1].contiguous() if aliased else None, clip=c)
+                               old_log_std=old_dev[-1].contiguous() if aliased else None, clip=c,
+                               wide=self.fit_backend == "hip_wide")
             else:
                 tr.epoch(("ppo", self._ncall), mb_loss, batches)
         tr.push()

@@ -1,13 +1,22 @@
 """PPO.train_from_paths on synthetic paths with fit_backend "torch" (a captured graph
-of torch ops per minibatch step) against "hip" (csrc/policy_fit.hip), at two shapes:
+of torch ops per minibatch step) against a fused backend ("hip", csrc/policy_fit.hip, or
+"hip_wide", csrc/policy_fit_wide.hip), at these shapes:
 
-    swimmer   n = 8, m = 2, hidden (64, 64), 25 paths of 500 rows, class defaults
-              (10 epochs of 195 minibatches of 64 rows: 1,950 Adam steps a call)
-    humanoid  n = 376, m = 17, hidden (64, 64), 100 paths of 1000 rows, epochs = 2
-              (3,124 steps a call)
+    swimmer      n = 8, m = 2, hidden (64, 64), 25 paths of 500 rows, class defaults
+                 (10 epochs of 195 minibatches of 64 rows: 1,950 Adam steps a call)
+    humanoid     n = 376, m = 17, hidden (64, 64), 100 paths of 1000 rows, epochs = 2
+                 (3,124 steps a call)
+    halfcheetah  n = 17, m = 6, hidden (128, 128), 100 paths of 1000 rows, epochs = 2
+                 (3,124 steps a call)
+    door         n = 39, m = 28, hidden (256, 256), 200 paths of 200 rows, epochs = 4
+                 (2,500 steps a call)
 
     python tools/policy_fit_bench.py [--alternations 3] [--timeout 300] [--shapes swimmer,humanoid]
-                                     [--algo ppo|bc_mse]
+                                     [--algo ppo|bc_mse] [--backends torch,hip] [--hidden H0,H1]
+
+--backends names the two backends that alternate (default torch,hip; torch,hip_wide for the wide
+shapes, hip,hip_wide to compare the two fused ones where both run); --hidden overrides the
+shapes' hidden sizes.
 
 --algo bc_mse times behavior_cloning_2.BC.train() (the MSE head, mjrl_policy_mse_epoch)
 instead, on synthetic expert paths of the same sizes: class defaults at swimmer (5
@@ -33,10 +42,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-SHAPES = {   # n, m, paths, rows per path, PPO keyword arguments
-    "swimmer": (8, 2, 25, 500, {}),
-    "humanoid": (376, 17, 100, 1000, dict(epochs=2)),
+SHAPES = {   # n, m, paths, rows per path, PPO keyword arguments, hidden sizes
+    "swimmer": (8, 2, 25, 500, {}, (64, 64)),
+    "humanoid": (376, 17, 100, 1000, dict(epochs=2), (64, 64)),
+    "halfcheetah": (17, 6, 100, 1000, dict(epochs=2), (128, 128)),
+    "door": (39, 28, 200, 200, dict(epochs=4), (256, 256)),
 }
+BACKENDS = ("torch", "hip", "hip_wide")
 
 
 def child(args):
@@ -46,8 +58,10 @@ def child(args):
     from mjrl_amd.algos.ppo_clip import PPO
     from mjrl_amd.policies.gaussian_mlp import MLP
     from mjrl_amd.utils.gym_env import EnvSpec
-    n, m, npaths, H, kw = SHAPES[args.shape]
-    policy = MLP(EnvSpec(n, m, H, 1), hidden_sizes=(64, 64), seed=1, init_log_std=-0.5)
+    n, m, npaths, H, kw, hidden = SHAPES[args.shape]
+    if args.hidden:
+        hidden = tuple(int(h) for h in args.hidden.split(","))
+    policy = MLP(EnvSpec(n, m, H, 1), hidden_sizes=hidden, seed=1, init_log_std=-0.5)
     mse = args.algo == "bc_mse"
     if mse:
         from mjrl_amd.algos.behavior_cloning_2 import BC
@@ -91,7 +105,7 @@ def child(args):
     steps = agent.epochs * int(npaths * H / agent.mb_size)
     theta = policy.get_param_values()
     print(json.dumps(dict(backend=args.child, shape=args.shape, call_s=times[1], epochs_s=epochs_s[1],
-                          warmup_s=times[0], steps=steps, param_norm=float(np.linalg.norm(theta)),
+                          warmup_s=times[0], steps=steps, hidden=list(hidden), param_norm=float(np.linalg.norm(theta)),
                           finite=bool(np.all(np.isfinite(theta))))))
 
 
@@ -102,20 +116,26 @@ def main():
     ap.add_argument("--shapes", default="swimmer,humanoid")
     ap.add_argument("--algo", choices=("ppo", "bc_mse"), default="ppo")
     ap.add_argument("--shape", default="swimmer", help=argparse.SUPPRESS)
-    ap.add_argument("--child", choices=("torch", "hip"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--backends", default="torch,hip", help="the two backends that alternate")
+    ap.add_argument("--hidden", default="", help="H0,H1 instead of the shapes' own hidden sizes")
+    ap.add_argument("--child", choices=BACKENDS, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(args)
-    res = dict(tool="policy_fit_bench", shapes={})
+    pair_of = tuple(args.backends.split(","))
+    if len(pair_of) != 2 or pair_of[0] == pair_of[1] or any(b not in BACKENDS for b in pair_of):
+        ap.error("--backends takes two different names of %s" % (BACKENDS,))
+    base, other = pair_of
+    res = dict(tool="policy_fit_bench", backends=list(pair_of), shapes={})
     if args.algo != "ppo":
         res["algo"] = args.algo
     for shape in args.shapes.split(","):
-        runs = {"torch": [], "hip": []}
-        steps, norm = 0, {}
+        runs = {base: [], other: []}
+        steps, norm, hidden = 0, {}, None
         for pair in range(args.alternations + 1):
-            for backend in ("torch", "hip"):
+            for backend in pair_of:
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", backend, "--shape", shape,
-                       "--algo", args.algo]
+                       "--algo", args.algo, "--hidden", args.hidden]
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
                 except subprocess.TimeoutExpired:
@@ -126,19 +146,20 @@ def main():
                 out = json.loads(r.stdout.strip().splitlines()[-1])
                 if not out["finite"]:
                     sys.exit("policy_fit_bench: the %s run left non-finite parameters; stopping" % backend)
-                steps, norm[backend] = out["steps"], out["param_norm"]
+                steps, norm[backend], hidden = out["steps"], out["param_norm"], out["hidden"]
                 if pair > 0:   # pair 0 is the warm-up pair
                     runs[backend].append((out["call_s"], out["epochs_s"]))
 
         def summary(xs):
             return dict(median=statistics.median(xs), min=min(xs), max=max(xs), runs=xs)
-        one = dict(steps=steps, param_norm=norm)
-        for k in ("torch", "hip"):
+        one = dict(steps=steps, hidden=hidden, param_norm=norm)
+        for k in pair_of:
             one[k + "_call_s"] = summary([c for c, _ in runs[k]])
             one[k + "_epochs_s"] = summary([e for _, e in runs[k]])
-        one["us_per_step"] = {k: 1e6 * one[k + "_epochs_s"]["median"] / max(steps, 1) for k in ("torch", "hip")}
-        one["speedup_epochs"] = one["torch_epochs_s"]["median"] / one["hip_epochs_s"]["median"]
-        one["speedup_call"] = one["torch_call_s"]["median"] / one["hip_call_s"]["median"]
+        one["us_per_step"] = {k: 1e6 * one[k + "_epochs_s"]["median"] / max(steps, 1) for k in pair_of}
+        # the first backend's median over the second's
+        one["speedup_epochs"] = one[base + "_epochs_s"]["median"] / one[other + "_epochs_s"]["median"]
+        one["speedup_call"] = one[base + "_call_s"]["median"] / one[other + "_call_s"]["median"]
         res["shapes"][shape] = one
     print(json.dumps(res))
 
