@@ -638,9 +638,10 @@ int mjrl_policy_mse_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, 
  * m / bs outside 1..64, h0 / h1 outside 1..256 or a null result), 16-byte aligned, of which
  * nothing but float [4 * 64 * 256], the last step's loss, means anything after a call.
  * Exact-f32 MFMA, every sum in one fixed order, no atomics: the same state and arguments give
- * the same bits, however nmb steps are split over calls (step0 advanced).  The sums are
- * ordered as these kernels order them, so the bits are not mjrl_policy_fit_epoch's at the
- * widths both take.  Never allocates, never synchronises.  MJRL_EINVAL before any launch for
+ * the same bits, however nmb steps are split over calls (step0 advanced).  The step's pieces
+ * are the ones mjrl_policy_fit_epoch runs (csrc/policy_step.h) and its sums are ordered alike:
+ * at the widths both take, the tested shapes leave that entry's bits.
+ * Never allocates, never synchronises.  MJRL_EINVAL before any launch for
  * what mjrl_policy_fit_epoch / mjrl_policy_mse_epoch refuse, with these width limits;
  * nmb == 0 is MJRL_OK without a launch. */
 int mjrl_policy_fit_wide_scratch(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int64_t* floats);

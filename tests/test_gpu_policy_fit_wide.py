@@ -2,7 +2,8 @@
 mjrl_policy_fit_wide_epoch, mjrl_policy_mse_wide_epoch; fit_backend = "hip_wide"): the four
 kernel tests of test_gpu_policy_fit.py and test_gpu_bc_mse.py through the wide entry points
 (one step's gradient and loss against float64 autograd, Adam against the float64 formula, the
-split of a run into calls bit for bit, masked rows), and the three classes on the reference's
+split of a run into calls bit for bit, masked rows), the narrow and the wide entry points bit for
+bit against each other at widths both accept, and the three classes on the reference's
 own runs at these widths (tests/golden/bc_wide.npz, bc2_wide.npz, ppo_wide.npz) against the
 fixture and against the torch backend."""
 import ctypes as C
@@ -12,8 +13,8 @@ import pytest
 import torch
 
 import test_gpu_bc_mse as M
-from test_gpu_policy_fit import (B1, B2, CLIP, EPS, EXTRA, LR, NAMES, STEP0, T, _steps, assert_gradient, f64_eval,
-                                 loss_of, make_state, same_bits, shapes, split)
+from test_gpu_policy_fit import (B1, B2, CLIP, EPS, EXTRA, LR, NAMES, STEP0, T, Net, _steps, assert_gradient,
+                                 f64_eval, loss_of, make_state, same_bits, shapes, split)
 from test_policy_fit_wide import ppo_wide_agent, ppo_wide_paths, run_bc_wide
 
 pytestmark = pytest.mark.gpu
@@ -213,6 +214,28 @@ def test_rows_out_of_range_are_masked(case):
     ref_g, ref_loss = reference(st, idx)
     check_gradient(st, parts(g[0], st), ref_g)
     np.testing.assert_allclose(float(loss[0]), ref_loss, rtol=1e-5)
+
+
+# (n, m, h0, h1, bs, head) at widths both backends accept, weight decay 1e-3, seed 1
+BOTH = [(13, 1, 7, 64, 1, "bc"), (20, 5, 33, 17, 64, "ppo"), (257, 3, 16, 48, 33, "ppo-aliased"),
+        (20, 5, 33, 17, 64, "mse")]
+
+
+@pytest.mark.parametrize("case", BOTH, ids=["n%d-m%d-h%dx%d-bs%d-%s" % c for c in BOTH])
+def test_narrow_and_wide_entry_points_leave_the_same_bits(case):
+    """Both backends keep one arithmetic contract (csrc/policy_step.h holds the shared pieces), and
+    at these widths they order every sum alike: three steps through mjrl_policy_fit_epoch /
+    mjrl_policy_mse_epoch and through the wide entry points leave the same parameters, moments,
+    gradients and losses, bit for bit."""
+    n, m, h0, h1, bs, head = case
+    mse = head == "mse"
+    st = make_state(n, m, h0, h1, bs, "bc" if mse else head, 1e-3, 1)
+    narrow, wide = (M.Net if mse else Net)(st), WideNet(dict(st, head=head))
+    (gn, ln), (gw, lw) = (net.epoch(st["perm"], 3, grads=True) for net in (narrow, wide))
+    same_bits(narrow.host(), wide.host())
+    same_bits([[gn, ln]], [[gw, lw]])
+    assert np.all(np.isfinite(gn)) and np.all(np.isfinite(ln)) and len(narrow.host()[0]) == (6 if mse else 7)
+    assert float(narrow.scratch[0].item()) == float(wide.scratch[LOSS_OFF].item()) == float(ln[2])
 
 
 # ---- the classes ------------------------------------------------------------------------------
