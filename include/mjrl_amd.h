@@ -236,6 +236,21 @@ int mjrl_quadratic_baseline_residual_f32(const float* obs, const float* obs_lo, 
 int mjrl_gather_rows(const void* src, int64_t row_bytes, const int64_t* idx, int64_t n, void* dst,
                      void* stream);
 
+/* ---- run tables: compaction of a chunked row pool (samplers/stream_staging.ChunkSink) ----
+ * runs [R][4] int64 on the device, each row {src_row, dst_row, nrows, t0}: a piece of
+ * a pool that is contiguous there and in the batch (a trajectory's rows inside one
+ * chunk).  mjrl_copy_runs: for every run, dst rows [dst_row, dst_row + nrows) = src
+ * rows [src_row, src_row + nrows), rows of row_bytes bytes (a positive multiple of 4);
+ * src [src_rows] rows, dst [dst_rows] rows; t0 is ignored.  No per-row index is read,
+ * and every run moves as the widest words (16, 8 or 4 bytes) that divide both of its
+ * byte addresses and its byte length.  Runs must not overlap in dst.  A run with
+ * nrows <= 0, or that leaves [0, src_rows) or [0, dst_rows), is skipped whole: nothing
+ * is written outside dst.  MJRL_EINVAL without a launch for a negative size, a
+ * row_bytes that is not a positive multiple of 4, or R > 0 with src, runs or dst
+ * null; R == 0 is MJRL_OK without a launch. */
+int mjrl_copy_runs(const void* src, int64_t row_bytes, const int64_t* runs, int64_t R, int64_t src_rows,
+                   int64_t dst_rows, void* dst, void* stream);
+
 /* ---- moments for whitening / stats (npg_cg.py:91, 97-102; dapg.py:70) ----
  * out[0] = sum(x - c), out[1] = sum((x - c)^2), out[2] = N, out[3] = min(x),
  * out[4] = max(x), out[5] = -min(x) over x[0..N-1] (out needs 6 doubles),
@@ -508,6 +523,17 @@ int mjrl_value_features_slots(const double* obs64, const int32_t* live, const in
  * time_tab or out null; T == 0 is MJRL_OK without a launch. */
 int mjrl_value_features_finish(const float* feat_pad, const int64_t* src_row, int64_t T, int32_t n, int64_t rows_cap,
                                int64_t H, const float* time_tab, float* out, void* stream);
+/* The same matrix from a chunked pool, where a row's place no longer gives its time
+ * index: out [T][n + 4] f32, and for row i of a run {src_row, dst_row, nrows, t0} of
+ * runs [R][4] (int64, device; mjrl_copy_runs' table) out[dst_row + i][0..n) =
+ * feat[src_row + i][0..n) and out[dst_row + i][n + j] = time_tab[(t0 + i) * 4 + j].
+ * feat [src_rows][n] f32, time_tab [H][4] f32.  A run with nrows <= 0, that leaves
+ * [0, src_rows) or [0, T), or with t0 < 0 or t0 + nrows > H is skipped whole.  The
+ * word widths are mjrl_value_features_finish's (n and the three base addresses).
+ * MJRL_EINVAL without a launch for a negative size, n <= 0, H <= 0, or R > 0 with
+ * feat, runs, time_tab or out null; R == 0 is MJRL_OK without a launch. */
+int mjrl_value_features_finish_runs(const float* feat, const int64_t* runs, int64_t R, int32_t n, int64_t src_rows,
+                                    int64_t T, int64_t H, const float* time_tab, float* out, void* stream);
 
 /* ---- MLPBaseline.fit's minibatch Adam steps (mjrl/baselines/mlp_baseline.py:83-96) ----
  * The value network Linear(n + 4, 128) - ReLU - Linear(128, 128) - ReLU -
@@ -692,6 +718,16 @@ int mjrl_host_stage_lo_paths_f64(const double* const* srcs, const int64_t* rows,
 int mjrl_host_stage_rows_f64x(const double* src, int64_t rows, int32_t n, float* const* dst_rows, float* cmin,
                               float* cmax, const double* coeffs, const int64_t* tidx, double* pred,
                               int32_t* inexact);
+/* mjrl_host_stage_rows_f64x with one range and one flag per environment slot (the
+ * sink of samples-mode sampling, which learns only later whether a trajectory is
+ * part of the batch): row i is folded into cmin / cmax [nslots][n] at row slot[i] and
+ * raises inexact[slot[i]] ([nslots]), by the same comparisons in the same row order,
+ * so folding the tables of the accepted trajectories afterwards gives the ranges of
+ * the one-table call on their rows.  cmin, cmax, inexact and slot are required;
+ * MJRL_EINVAL as above, and for a slot[i] outside [0, nslots). */
+int mjrl_host_stage_rows_slots_f64x(const double* src, int64_t rows, int32_t n, float* const* dst_rows,
+                                    const int64_t* slot, int64_t nslots, float* cmin, float* cmax,
+                                    const double* coeffs, const int64_t* tidx, double* pred, int32_t* inexact);
 /* The extras of mjrl_host_stage_paths_f64x for one array through the portable loop
  * (tests compare it with the vector path). */
 int mjrl_host_extras_portable(const double* src, int64_t rows, int32_t n, const double* coeffs, double* pred,

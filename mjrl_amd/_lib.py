@@ -133,6 +133,7 @@ SIGNATURES = {
     "mjrl_cg_update": [I32, P, P, P, P, P, P, F32, P],
     "mjrl_scale_vec": [P, I32, F64, P, P],
     "mjrl_gather_rows": [P, I64, P, I64, P, P],
+    "mjrl_copy_runs": [P, I64, P, I64, I64, I64, P, P],
     "mjrl_linear_baseline_gram_scratch": [I32, I64, C.POINTER(I64)],
     "mjrl_linear_baseline_gram": [P, P, I64, I32, P, I64, P, P, P],
     "mjrl_linear_baseline_residual": [P, P, I64, I32, P, I64, P, P, P, P],
@@ -151,6 +152,7 @@ SIGNATURES = {
     "mjrl_policy_mean_slots": [SP, P, P, I64, I64, P, P, P, P, P, P, P],
     "mjrl_value_features_slots": [P, P, P, I64, I64, I32, I64, P, P],
     "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
+    "mjrl_value_features_finish_runs": [P, P, I64, I32, I64, I64, I64, P, P, P],
     "mjrl_value_mlp_scratch": [I32, I32, C.POINTER(I64)],
     "mjrl_value_mlp_epoch": [P, P, I64, I32, P, I64, I32, C.POINTER(ValueNet), C.POINTER(Adam), P, P, P, P],
     "mjrl_policy_fit_scratch": [I32, I32, I32, I32, I32, C.POINTER(I64)],
@@ -171,6 +173,7 @@ SIGNATURES = {
     "mjrl_host_stage_lo_paths_f64": [P, P, I32, I32, P],
     "mjrl_host_extras_portable": [P, I64, I32, P, P, P],
     "mjrl_host_stage_rows_f64x": [P, I64, I32, P, P, P, P, P, P, P],
+    "mjrl_host_stage_rows_slots_f64x": [P, I64, I32, P, P, I64, P, P, P, P, P, P],
     "mjrl_host_stage_f64_portable": [P, I64, I32, P, P, P],
     "mjrl_host_stage_avx512": [],
     "mjrl_host_gather": [P, P, I32, P],
@@ -212,7 +215,7 @@ def load(path=None):
 STAGE_LIB_PATH = os.path.join(HERE, "lib", "libmjrl_stage.so")
 STAGE_FUNCS = ("mjrl_host_stage_f64", "mjrl_host_stage_f32", "mjrl_host_stage_paths_f64",
                "mjrl_host_stage_paths_f64x", "mjrl_host_stage_lo_paths_f64", "mjrl_host_extras_portable",
-               "mjrl_host_stage_rows_f64x",
+               "mjrl_host_stage_rows_f64x", "mjrl_host_stage_rows_slots_f64x",
                "mjrl_host_stage_f64_portable", "mjrl_host_stage_avx512", "mjrl_host_gather")
 _STAGE = None
 

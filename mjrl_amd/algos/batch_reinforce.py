@@ -227,7 +227,11 @@ class BatchREINFORCE:
             quit()
         pool = self._pool()
         comm = self.comm() if pool is None else LocalComm()
-        vector = sample_mode == "trajectories" and comm.world_size == 1 and self._sampler_kind() == "vector"
+        # the vector sampler serves both modes on one process ("samples": the one-core
+        # loop of batch_sampler.py:58-103, lock-stepped; samplers/samples_schedule.py);
+        # sharded and pooled steps keep the reference samplers
+        vector = comm.world_size == 1 and self._sampler_kind() == "vector" and \
+            (sample_mode == "trajectories" or pool is None)
         trajectory_sampler, batch_sampler = (None, None) if vector else _samplers()
         ts = timer.time()
         if comm.world_size > 1:
@@ -245,19 +249,23 @@ class BatchREINFORCE:
             feats = self.staging_dtype is None and hasattr(self.baseline, "predict_features_device")
             if self.stream_staging and (self.staging_obs_dtype() == np.float32 or feats) \
                     and self._demo_paths() is None:
-                from ..samplers.stream_staging import StreamSink
+                from ..samplers.stream_staging import ChunkSink, StreamSink
+                # "samples": the number of paths is not known in advance, the sink is
+                # sized by rows (its first argument is then N timesteps)
+                Sink = StreamSink if sample_mode == "trajectories" else ChunkSink
 
                 def sink(n_paths, horizon, nslots):
-                    sinks.append(StreamSink(self.policy.n, self.policy.m, horizon, n_paths, self.engine().device,
-                                            baseline=self.baseline, nslots=nslots, value_features=feats))
+                    sinks.append(Sink(self.policy.n, self.policy.m, horizon, n_paths, self.engine().device,
+                                      baseline=self.baseline, nslots=nslots, value_features=feats))
                     return sinks[-1]
             else:
                 sink = None
             paths = sample_paths_vectorized(N, self.policy, T, env=self.env_factory, env_name=env_name,
                                             pegasus_seed=self.seed, num_envs=self.num_envs,
                                             device=self.engine().device, sink=sink,
-                                            num_workers=self._sampler_workers())
-            if sinks:
+                                            num_workers=self._sampler_workers(), sample_mode=sample_mode)
+            # a sink whose pool overflowed is dropped: the batch is staged from the paths
+            if sinks and not getattr(sinks[0], "overflowed", False):
                 self._stream = sinks[0]
         elif sample_mode == "trajectories":
             paths = trajectory_sampler.sample_paths_parallel(N, self.policy, T, env_name, self.seed, num_cpu)

@@ -1100,6 +1100,100 @@ __global__ void __launch_bounds__(256) k_gather_rows(const V* __restrict__ src, 
     }
 }
 
+// ---- run tables (the chunked row pool of samplers/stream_staging.ChunkSink) ----
+// runs [R][4] int64: {src_row, dst_row, nrows, t0}.  A run is one contiguous piece
+// of a pool (a trajectory's rows inside one chunk) and one contiguous piece of the
+// batch: no per-row index, and the words of a run are consecutive in both.
+struct RunSpan {
+    int64_t src, dst, rows, t0;
+    bool ok;
+};
+
+// Run r, or ok = false when it leaves [0, src_rows) or [0, dst_rows) or is empty
+// (the comparisons are written so that no sum of two row numbers can overflow).
+__device__ __forceinline__ RunSpan load_run(const int64_t* __restrict__ runs, int64_t r, int64_t src_rows,
+                                            int64_t dst_rows) {
+    RunSpan s;
+    s.src = runs[4 * r], s.dst = runs[4 * r + 1], s.rows = runs[4 * r + 2], s.t0 = runs[4 * r + 3];
+    s.ok = s.rows > 0 && s.src >= 0 && s.dst >= 0 && s.rows <= src_rows && s.rows <= dst_rows &&
+           s.src <= src_rows - s.rows && s.dst <= dst_rows - s.rows;
+    return s;
+}
+
+template <typename V>
+__device__ __forceinline__ void copy_words(const char* __restrict__ s, char* __restrict__ d, int64_t nbytes) {
+    const V* __restrict__ sv = reinterpret_cast<const V*>(s);
+    V* __restrict__ dv = reinterpret_cast<V*>(d);
+    const int64_t nw = nbytes / (int64_t)sizeof(V), step = (int64_t)gridDim.x * blockDim.x;
+    int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; w + 3 * step < nw; w += 4 * step) {   // four loads in flight per lane
+        const V a = sv[w], b = sv[w + step], c = sv[w + 2 * step], d = sv[w + 3 * step];
+        dv[w] = a, dv[w + step] = b, dv[w + 2 * step] = c, dv[w + 3 * step] = d;
+    }
+    for (; w < nw; w += step) dv[w] = sv[w];
+}
+
+// dst rows [dst_row, dst_row + nrows) = src rows [src_row, src_row + nrows) for every
+// run.  blockIdx.y walks the runs, the gridDim.x workgroups of a run its words: lane
+// i of a wave at word base + i, so a wave moves 1 KiB per instruction with 16-byte
+// words.  The width is the run's own (a wave-uniform choice): the widest of 16 / 8 /
+// 4 bytes that divides both of its byte addresses and its byte length.
+__global__ void __launch_bounds__(256) k_copy_runs(const char* __restrict__ src, int64_t row_bytes,
+                                                   const int64_t* __restrict__ runs, int64_t R, int64_t src_rows,
+                                                   int64_t dst_rows, char* __restrict__ dst) {
+    for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
+        const RunSpan s = load_run(runs, r, src_rows, dst_rows);
+        if (!s.ok) continue;
+        const char* __restrict__ sp = src + s.src * row_bytes;
+        char* __restrict__ dp = dst + s.dst * row_bytes;
+        const int64_t nbytes = s.rows * row_bytes;
+        const uintptr_t a = (uintptr_t)sp | (uintptr_t)dp | (uintptr_t)nbytes;
+        if (a % 16 == 0)
+            copy_words<float4>(sp, dp, nbytes);
+        else if (a % 8 == 0)
+            copy_words<float2>(sp, dp, nbytes);
+        else
+            copy_words<float>(sp, dp, nbytes);
+    }
+}
+
+// out [T][n + 4]: row dst_row + i of a run = [feat[src_row + i][0..n), time_tab[t0 + i][0..4)].
+// k_value_features_finish's row body (rollout.hip: one wave per row, V = float4 /
+// float2 / float words chosen by the host from n and the base addresses), with the
+// time index carried by the run instead of r % H.  blockIdx.y walks the runs, the
+// waves of gridDim.x workgroups a run's rows.  A run that leaves the pools or the
+// time table is skipped whole.
+template <typename V>
+__global__ void __launch_bounds__(256) k_value_features_finish_runs(const V* __restrict__ feat,
+                                                                    const int64_t* __restrict__ runs, int64_t R,
+                                                                    int nv, int64_t src_rows, int64_t T, int64_t H,
+                                                                    const V* __restrict__ time_tab,
+                                                                    V* __restrict__ out) {
+    constexpr int TV = 16 / (int)sizeof(V);   // words of V per time_tab row (4 floats)
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
+        const RunSpan s = load_run(runs, r, src_rows, T);
+        if (!s.ok || s.t0 < 0 || s.rows > H || s.t0 > H - s.rows) continue;
+        for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < s.rows; i += nw) {
+            const V* __restrict__ f = feat + (s.src + i) * nv;
+            const V* __restrict__ tt = time_tab + (s.t0 + i) * TV;
+            V* __restrict__ d = out + (s.dst + i) * (nv + TV);
+            for (int c = lane; c < nv + TV; c += 64) d[c] = c < nv ? f[c] : tt[c - nv];
+        }
+    }
+}
+
+// The grid of a run-table kernel: one y per run (up to the grid limit; the kernels
+// stride past it), and enough x workgroups per run that a short table still fills
+// the device while a long one does not multiply its workgroups.
+static dim3 runs_grid(int64_t R) {
+    const int64_t gy = R < 65535 ? R : 65535;
+    int64_t gx = (16384 + gy - 1) / gy;
+    gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
+    return dim3((unsigned)gx, (unsigned)gy);
+}
+
 // The same returns / advantages / path-return sums as k_gae by a wave-parallel
 // scan (the north_star's "wavefront shuffles for the GAE prefix scan"): the
 // recurrence y_t = x_t + c y_{t+1} is the composition of affine maps
@@ -1522,6 +1616,36 @@ int mjrl_gather_rows(const void* src, int64_t row_bytes, const int64_t* idx, int
     else
         hipLaunchKernelGGL(k_gather_rows<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)src,
                            row_bytes / 4, idx, n, (float*)dst);
+    return err(hipGetLastError());
+}
+
+int mjrl_copy_runs(const void* src, int64_t row_bytes, const int64_t* runs, int64_t R, int64_t src_rows,
+                   int64_t dst_rows, void* dst, void* stream) {
+    if (R < 0 || src_rows < 0 || dst_rows < 0 || row_bytes <= 0 || row_bytes % 4 != 0) return MJRL_EINVAL;
+    if (R > 0 && (!src || !runs || !dst)) return MJRL_EINVAL;
+    if (R == 0) return MJRL_OK;
+    hipLaunchKernelGGL(k_copy_runs, runs_grid(R), dim3(256), 0, (hipStream_t)stream, (const char*)src, row_bytes,
+                       runs, R, src_rows, dst_rows, (char*)dst);
+    return err(hipGetLastError());
+}
+
+int mjrl_value_features_finish_runs(const float* feat, const int64_t* runs, int64_t R, int32_t n, int64_t src_rows,
+                                    int64_t T, int64_t H, const float* time_tab, float* out, void* stream) {
+    if (R < 0 || T < 0 || n <= 0 || src_rows < 0 || H <= 0) return MJRL_EINVAL;
+    if (R > 0 && (!feat || !runs || !time_tab || !out)) return MJRL_EINVAL;
+    if (R == 0) return MJRL_OK;
+    const dim3 g = runs_grid(R);
+    const uintptr_t a = (uintptr_t)feat | (uintptr_t)time_tab | (uintptr_t)out;
+    hipStream_t st = (hipStream_t)stream;
+    if (n % 4 == 0 && a % 16 == 0)
+        hipLaunchKernelGGL(k_value_features_finish_runs<float4>, g, dim3(256), 0, st, (const float4*)feat, runs, R,
+                           n / 4, src_rows, T, H, (const float4*)time_tab, (float4*)out);
+    else if (n % 2 == 0 && a % 8 == 0)
+        hipLaunchKernelGGL(k_value_features_finish_runs<float2>, g, dim3(256), 0, st, (const float2*)feat, runs, R,
+                           n / 2, src_rows, T, H, (const float2*)time_tab, (float2*)out);
+    else
+        hipLaunchKernelGGL(k_value_features_finish_runs<float>, g, dim3(256), 0, st, feat, runs, R, (int)n, src_rows,
+                           T, H, time_tab, out);
     return err(hipGetLastError());
 }
 

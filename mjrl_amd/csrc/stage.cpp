@@ -382,6 +382,41 @@ int mjrl_host_stage_rows_f64x(const double* src, int64_t rows, int32_t n, float*
     return MJRL_OK;
 }
 
+// mjrl_host_stage_rows_f64x with the ranges and the exactness flag kept per
+// environment slot (cmin / cmax [nslots][n], inexact [nslots]; row i belongs to
+// slot[i]): the samples-mode sink folds a trajectory's table into the batch's only
+// once the trajectory is known to be part of it.  The same comparisons and the same
+// per-row extras as above.
+int mjrl_host_stage_rows_slots_f64x(const double* src, int64_t rows, int32_t n, float* const* dst_rows,
+                                    const int64_t* slot, int64_t nslots, float* cmin, float* cmax,
+                                    const double* coeffs, const int64_t* tidx, double* pred, int32_t* inexact) {
+    if (rows < 0 || n <= 0 || nslots < 0 || (rows > 0 && (!src || !dst_rows || !slot))) return MJRL_EINVAL;
+    if (!cmin || !cmax || !inexact || (coeffs == nullptr) != (pred == nullptr)) return MJRL_EINVAL;
+    if (coeffs && !tidx) return MJRL_EINVAL;
+    const bool vec = have_avx512();
+    for (int64_t i = 0; i < rows; ++i) {
+        const double* s = src + i * n;
+        float* d = dst_rows[i];
+        if (!d || slot[i] < 0 || slot[i] >= nslots) return MJRL_EINVAL;
+        float* lo = cmin + slot[i] * n;
+        float* hi = cmax + slot[i] * n;
+        for (int32_t k = 0; k < n; ++k) {
+            const float v = (float)s[k];
+            d[k] = v;
+            const float l = lo[k], h = hi[k];
+            lo[k] = v < l ? v : l;   // a NaN compares false: skipped (as the block pass)
+            hi[k] = v > h ? v : h;
+        }
+        const int64_t t = tidx ? tidx[i] : 0;
+        bool bad = false;
+        __mmask8 badv = 0;
+        const double p = vec ? row_extras_avx512(s, t, n, coeffs, badv) : row_extras_portable(s, t, n, coeffs, bad);
+        if (pred) pred[i] = p;
+        if (bad || badv) inexact[slot[i]] = 1;
+    }
+    return MJRL_OK;
+}
+
 // The extras alone through the portable loop, whatever the CPU (tests compare the paths).
 int mjrl_host_extras_portable(const double* src, int64_t rows, int32_t n, const double* coeffs, double* pred,
                               int32_t* inexact) {

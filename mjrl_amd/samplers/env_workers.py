@@ -46,6 +46,8 @@ from multiprocessing import connection, shared_memory
 
 import numpy as np
 
+from .samples_schedule import SamplesSchedule
+
 RUNNING, ENDED, ENDED_DONE = 0, 1, 2   # the done board
 
 
@@ -318,17 +320,22 @@ def close_env_pools():
             pass
 
 
-def sample_paths(pool, N, means, log_std, T=1e6, pegasus_seed=None, sink=None):
-    """N trajectories on the pool's slots; the paths of vector_sampler's in-process
-    loop for the same arguments.
+def sample_paths(pool, N, means, log_std, T=1e6, pegasus_seed=None, sink=None, sample_mode="trajectories"):
+    """N trajectories (sample_mode="samples": the shortest prefix of trajectories
+    with at least N timesteps, samples_schedule.py) on the pool's slots; the paths of
+    vector_sampler's in-process loop for the same arguments.
 
     means(obs [S][n] f64, live int32 [E], out=mean [S][m] f32): the mean provider;
     it writes rows `live` of out (BatchedPolicy.means_slots in production, any
     row-wise forward in a test).  log_std: the policy's log_std_val (f64 [m]).
     sink: as sample_paths_vectorized's."""
     S, n, m = pool.S, pool.n, pool.m
+    if sample_mode not in ("trajectories", "samples"):
+        raise ValueError("sample_mode must be 'trajectories' or 'samples', got %r" % (sample_mode,))
     if N <= 0:
         return []
+    if sample_mode == "samples" and pegasus_seed is None:
+        pegasus_seed = 0   # batch_sampler.py:87
     if S != min(S, int(N)):
         raise ValueError("a pool of %d slots for %d trajectories" % (S, N))
     horizon = min(T, pool.horizon)
@@ -340,13 +347,14 @@ def sample_paths(pool, N, means, log_std, T=1e6, pegasus_seed=None, sink=None):
                          % (sink.N, sink.H, len(sink.buf), N, horizon, S))
     log_std = np.float64(log_std)
     try:
-        return _sample(pool, int(N), means, log_std, horizon, H, pegasus_seed, sink)
+        return _sample(pool, int(N), means, log_std, horizon, H, pegasus_seed, sink,
+                       SamplesSchedule(N) if sample_mode == "samples" else None)
     except BaseException:
         pool._abort()
         raise
 
 
-def _sample(pool, N, means, log_std, horizon, H, seed, sink):
+def _sample(pool, N, means, log_std, horizon, H, seed, sink, sched=None):
     S, n, m = pool.S, pool.n, pool.m
     v = pool.v
     obs_b, mean_b, act_b, rew_b, done_b = v["obs"], v["mean"], v["act"], v["rew"], v["done"]
@@ -355,7 +363,10 @@ def _sample(pool, N, means, log_std, horizon, H, seed, sink):
     h_rew, h_mean = np.empty((S, H)), np.empty((S, H, m), np.float32)
     ep = np.full(S, -1, np.int64)
     t = np.zeros(S, np.int64)
-    paths = [None] * N
+    # samples mode (sched): the paths and the streams' final states by trajectory
+    # index, until the schedule knows which prefix is the batch
+    paths = {} if sched is not None else [None] * N
+    states = {}
     last_state = None
     next_ep = 0
     pool.begin(dict(seed=seed, scale=np.exp(log_std), horizon=horizon))
@@ -364,9 +375,11 @@ def _sample(pool, N, means, log_std, horizon, H, seed, sink):
         nonlocal next_ep
         items = []
         for s in slots:
-            if next_ep >= N:
+            if (not sched.may_start()) if sched is not None else next_ep >= N:
                 ep[s] = -1
                 continue
+            if sched is not None:
+                next_ep = sched.start()
             ep[s], t[s] = next_ep, 0
             items.append((s, next_ep))
             if sink is not None:
@@ -401,6 +414,9 @@ def _sample(pool, N, means, log_std, horizon, H, seed, sink):
             for s, ts, r in zip(live.tolist(), tl.tolist(), rl.tolist()):
                 sink.reward(s, ts, r)
         t[live] += 1
+        if sched is not None:
+            for k in ep[live].tolist():
+                sched.step(k)
         flagged = live[done_b[live] != RUNNING].tolist()
         if flagged != sorted(ended):
             raise RuntimeError("mjrl_amd env workers: the done board (slots %s) and the workers' replies (slots %s) "
@@ -416,8 +432,20 @@ def _sample(pool, N, means, log_std, horizon, H, seed, sink):
                                 agent_infos=dict(mean=mean.copy(), log_std=np.array([log_std] * L),
                                                  evaluation=mean.copy()),
                                 env_infos=einfo, terminated=done)
-            if ep[s] == N - 1:
+            if sched is not None:
+                states[int(ep[s])] = state
+                sched.end(int(ep[s]))
+            elif ep[s] == N - 1:
                 last_state = state
+        if sched is not None and sched.done:
+            # the prefix 0..K is the batch; what is still live lies above K (the next
+            # call's `start` clears the workers' live sets)
+            for s in np.nonzero(ep >= 0)[0].tolist():
+                if s not in ended and sink is not None:
+                    sink.abandon(s)
+            paths = [paths[k] for k in range(sched.accepted)]
+            last_state = states[sched.K]
+            break
         parity ^= 1
         items = assign(flagged)
         if items:

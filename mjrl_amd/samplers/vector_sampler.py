@@ -24,6 +24,7 @@ import torch
 
 from .. import _lib
 from ..engine import UpdateEngine
+from .samples_schedule import SamplesSchedule
 
 
 class BatchedPolicy:
@@ -152,8 +153,19 @@ def _with_board(sink, bp, S):
 
 
 def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_seed=None, num_envs=64,
-                            device=None, sink=None, num_workers=0, worker_timeout=900.0):
+                            device=None, sink=None, num_workers=0, worker_timeout=900.0,
+                            sample_mode="trajectories"):
     """N trajectories on min(num_envs, N) lock-stepped environments.
+
+    sample_mode="samples": N is a number of timesteps, and the paths returned are
+    those of the reference's one-core loop (batch_sampler.py:58-103), whatever
+    num_envs and num_workers are: trajectory k is the rollout seeded s0 + k (s0 =
+    pegasus_seed, or 0 when it is None), and the list is the shortest prefix 0..K
+    whose lengths sum to >= N ([] for N <= 0).  samples_schedule.py holds the rule
+    by which trajectories start and sampling stops; a live trajectory with an
+    index above K is abandoned (sink.abandon(slot)), and numpy's global RNG is left
+    as trajectory K left it.  The sink is then one sized by rows
+    (stream_staging.ChunkSink; the factory receives N timesteps).
 
     env: an environment factory (called once per slot) or None with env_name
     (mjrl.utils.get_environment, the reference's registry).  sink: a
@@ -176,6 +188,11 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
     are 1-D f64 arrays and whose rewards are Python floats (other dtypes and
     shapes are kept as they are by num_workers=0 only).  worker_timeout: the
     seconds any wait for the workers may take before the pool is torn down."""
+    if sample_mode not in ("trajectories", "samples"):
+        raise ValueError("sample_mode must be 'trajectories' or 'samples', got %r" % (sample_mode,))
+    samples = sample_mode == "samples"
+    if samples and pegasus_seed is None:
+        pegasus_seed = 0   # batch_sampler.py:87
     if num_workers:
         if env is None and env_name is None:
             raise ValueError("sample_paths_vectorized needs env (a factory) or env_name")
@@ -187,7 +204,7 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
         bp = BatchedPolicy(policy, device)
         pool.register_host()
         return env_workers.sample_paths(pool, N, bp.means_slots, bp.log_std_val, T, pegasus_seed,
-                                        _with_board(sink, bp, pool.S))
+                                        _with_board(sink, bp, pool.S), sample_mode=sample_mode)
     if env is None:
         if env_name is None:
             raise ValueError("sample_paths_vectorized needs env (a factory) or env_name")
@@ -211,16 +228,26 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
                          % (sink.N, sink.H, len(sink.buf), N, horizon, len(slots)))
     for i, s in enumerate(slots):
         s.idx = i
-    paths = [None] * N
+    # samples mode: the paths and the streams' final states by trajectory index,
+    # until the schedule knows which prefix is the batch
+    sched = SamplesSchedule(N) if samples else None
+    paths = {} if samples else [None] * N
+    states = {}
     last_state = [None]
     next_ep = [0]
 
     def start(s):
-        if next_ep[0] >= N:
-            s.ep = None
-            return
-        s.ep = ep = next_ep[0]
-        next_ep[0] += 1
+        if sched is not None:
+            if not sched.may_start():
+                s.ep = None
+                return
+            s.ep = ep = sched.start()
+        else:
+            if next_ep[0] >= N:
+                s.ep = None
+                return
+            s.ep = ep = next_ep[0]
+            next_ep[0] += 1
         if pegasus_seed is not None:
             _seed_env(s.env, pegasus_seed + ep)
             s.rs = np.random.RandomState(pegasus_seed + ep)
@@ -242,7 +269,10 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
             sink.finish(s.idx, s.t, bool(done))
         paths[s.ep] = dict(observations=np.array(s.obs), actions=np.array(s.act), rewards=np.array(s.rew),
                            agent_infos=_stack(s.ainfo), env_infos=_stack(s.einfo), terminated=done)
-        if s.ep == N - 1:
+        if sched is not None:
+            states[s.ep] = s.rs.get_state()
+            sched.end(s.ep)
+        elif s.ep == N - 1:
             last_state[0] = s.rs.get_state()
         start(s)
 
@@ -272,8 +302,19 @@ def sample_paths_vectorized(N, policy, T=1e6, env=None, env_name=None, pegasus_s
             s.einfo.append(info)
             s.o = next_o
             s.t += 1
+            if sched is not None:
+                sched.step(s.ep)
             if done == True or s.t >= horizon:   # noqa: E712 (base_sampler.py:61: done != True)
                 finish(s, done)
+        if sched is not None and sched.done:
+            break
+    if sched is not None:
+        # the prefix 0..K is the batch; what is still live lies above K
+        for s in slots:
+            if s.ep is not None and sink is not None:
+                sink.abandon(s.idx)
+        paths = [paths[k] for k in range(sched.accepted)]
+        last_state[0] = states[sched.K]
     if last_state[0] is not None:
         np.random.set_state(last_state[0])
     return paths
