@@ -535,6 +535,51 @@ int mjrl_value_features_finish(const float* feat_pad, const int64_t* src_row, in
 int mjrl_value_features_finish_runs(const float* feat, const int64_t* runs, int64_t R, int32_t n, int64_t src_rows,
                                     int64_t T, int64_t H, const float* time_tab, float* out, void* stream);
 
+/* ---- step-major device rollouts cut into the path-major batch (csrc/ingest.hip) ----
+ * A batched simulator with auto-reset environments leaves obs [H][E][n], act
+ * [H][E][m], rew [H][E] and done [H][E] in device memory.  The cut, defined once:
+ * env e has steps[e] valid steps (steps null: H; a value outside [0, H] is clamped),
+ * and a cell (t, e) with t >= steps[e] is never read.  Env e's valid steps are cut
+ * after every cell with done != 0; that path's flag is terminated[t][e] != 0
+ * (terminated null: 1).  A non-empty remainder is a last path with flag 0.  Paths are
+ * ordered env-ascending, then time-ascending: the row of cell (t, e) is R[e] + t, R
+ * the exclusive prefix sum of steps.
+ *
+ * mjrl_rollout_segments writes env_row [E + 1] = R (env_row[E] = T), the P + 1 first
+ * entries of path_off [path_cap + 1] (path_off[P] = T), the P first entries of
+ * path_term [path_cap] and counts [2] = {P, T}; entries past those are left as they
+ * were, and nothing at or beyond path_cap is written (P <= T, so path_cap = T always
+ * holds the table).  done / terminated are bytes (u8 or bool), steps [E] int64,
+ * scratch mjrl_rollout_segments_scratch(E) int64 words; all device pointers.  Three
+ * launches (count, scan, write), integer sums in one fixed order.  MJRL_EINVAL for a
+ * negative size, a null env_row, path_off or counts, E > 0 with scratch null (or done
+ * null when H > 0), or path_cap > 0 with path_term null. */
+int mjrl_rollout_segments_scratch(int64_t E, int64_t* words);
+int mjrl_rollout_segments(const uint8_t* done, const uint8_t* terminated, const int64_t* steps, int64_t H, int64_t E,
+                          int64_t path_cap, int64_t* env_row, int64_t* path_off, uint8_t* path_term, int64_t* counts,
+                          int64_t* scratch, void* stream);
+/* The transposing pack: row R[e] + t of obs_out [T][n], act_out [T][m] and rew_out [T]
+ * receives obs[t][e][:], act[t][e][:] and rew[t][e], for every valid cell.
+ * Observations and actions are f32 (obs_f64 = 0) or f64 (1) and keep their bits;
+ * rewards are f32 (rew_f64 = 0) or f64 and leave as f64 (the widening is exact).  With
+ * steps null every env has H rows and T must be H E; else env_row is R as
+ * mjrl_rollout_segments wrote it: a row whose cell (found by bisection of env_row)
+ * lies outside env e's valid steps is skipped, never dereferenced.  Rows move as
+ * 16-byte words where the row bytes and the base addresses allow, else 8 or 4.
+ * obs_range (nullable; f32 observations only): f32 [2][n], the per-column (min, max)
+ * over the T rows by the host staging pass's comparisons (mjrl_host_stage_f32: a NaN
+ * is skipped, an empty or all-NaN column stays (+inf, -inf)), the input of
+ * mjrl_obs_colscale_range; per-workgroup partials in scratch
+ * (mjrl_rollout_pack_scratch(T, n) floats, 16-byte aligned), then one fixed-order
+ * reduce.  MJRL_EINVAL for a negative size, n or m <= 0, a flag other than 0 / 1,
+ * T > 0 with a null array or H E == 0, steps without env_row, steps null with
+ * T != H E, obs_range with obs_f64 or without scratch. */
+int mjrl_rollout_pack_scratch(int64_t T, int32_t n, int64_t* floats);
+int mjrl_rollout_pack(const void* obs, const void* act, const void* rew, int32_t obs_f64, int32_t rew_f64,
+                      const int64_t* steps, const int64_t* env_row, int64_t H, int64_t E, int32_t n, int32_t m,
+                      int64_t T, void* obs_out, void* act_out, double* rew_out, float* obs_range, float* scratch,
+                      void* stream);
+
 /* ---- MLPBaseline.fit's minibatch Adam steps (mjrl/baselines/mlp_baseline.py:83-96) ----
  * The value network Linear(n + 4, 128) - ReLU - Linear(128, 128) - ReLU -
  * Linear(128, 1) and its Adam state, device pointers in torch's parameter order

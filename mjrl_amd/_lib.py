@@ -153,6 +153,10 @@ SIGNATURES = {
     "mjrl_value_features_slots": [P, P, P, I64, I64, I32, I64, P, P],
     "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
     "mjrl_value_features_finish_runs": [P, P, I64, I32, I64, I64, I64, P, P, P],
+    "mjrl_rollout_segments_scratch": [I64, C.POINTER(I64)],
+    "mjrl_rollout_segments": [P, P, P, I64, I64, I64, P, P, P, P, P, P],
+    "mjrl_rollout_pack_scratch": [I64, I32, C.POINTER(I64)],
+    "mjrl_rollout_pack": [P, P, P, I32, I32, P, P, I64, I64, I32, I32, I64, P, P, P, P, P, P],
     "mjrl_value_mlp_scratch": [I32, I32, C.POINTER(I64)],
     "mjrl_value_mlp_epoch": [P, P, I64, I32, P, I64, I32, C.POINTER(ValueNet), C.POINTER(Adam), P, P, P, P],
     "mjrl_policy_fit_scratch": [I32, I32, I32, I32, I32, C.POINTER(I64)],

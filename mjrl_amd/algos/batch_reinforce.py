@@ -424,6 +424,60 @@ class BatchREINFORCE:
                                        pre=self.__dict__.pop("_pre", None))
         return self._update(batch, paths)
 
+    def train_from_rollout(self, observations, actions, rewards, done, terminated=None, steps=None, gamma=0.995,
+                           gae_lambda=0.98, fit_baseline=True):
+        """One update from a step-major rollout that is already in GPU memory
+        (a batched simulator, a replay of logged data, another library's sampler):
+        observations [H][E][n], actions [H][E][m], rewards [H][E], done [H][E] and
+        optionally terminated [H][E] as torch tensors on the engine's GPU, steps a
+        host sequence of valid steps per env (DeviceBatch.from_rollout has the
+        layout and the cut; every path is a trajectory of its own).  Nothing goes
+        through the host: the rollout is cut and packed on the device, then
+        returns + GAE + the update as train_from_samples runs them, then (with
+        fit_baseline) the LinearBaseline fit from the rows and returns still in
+        HBM.  Returns [mean, std, min, max] of the path returns.  For the path
+        dicts (logging, evaluate_success) see samplers.rollout_ingest.rollout_to_paths.
+        BatchREINFORCE, NPG and TRPO with a LinearBaseline, a ZeroBaseline or no
+        baseline, on one GPU in this process."""
+        for k in type(self).__mro__:
+            if k.__name__ == "DAPG":
+                raise ValueError("%s.train_from_rollout: DAPG's demonstration rows are host paths; use train_step / "
+                                 "train_from_paths" % type(self).__name__)
+            if k.__name__ == "PPO":
+                raise ValueError("%s.train_from_rollout: PPO's update works on path dicts; use train_from_paths "
+                                 "(rollout_ingest.rollout_to_paths makes them)" % type(self).__name__)
+        from ..comm import launched_world
+        from ..pool import resolve_devices
+        lw = launched_world()
+        if self._comm is None and lw is None and resolve_devices(getattr(self, "_devices", None)) is not None:
+            raise ValueError("%s.train_from_rollout: a devices= pool (or MJRL_AMD_DEVICES) shards host paths over "
+                             "worker processes; a device rollout is updated on the GPU that holds it"
+                             % type(self).__name__)
+        world = self._comm.world_size if self._comm is not None else (lw[1] if lw is not None else 1)
+        if world > 1:
+            raise ValueError("%s.train_from_rollout: world size %d: sharded runs take host paths (train_step)"
+                             % (type(self).__name__, world))
+        DeviceBatch.check_rollout(observations, actions, rewards, done, terminated, steps, self.baseline)
+        if self.comm().world_size > 1:   # a process group initialised by the caller
+            raise ValueError("%s.train_from_rollout: world size %d: sharded runs take host paths (train_step)"
+                             % (type(self).__name__, self.comm().world_size))
+        eng = self.engine()
+        if observations.device != eng.device:
+            raise ValueError("%s.train_from_rollout: the rollout is on %s, the agent's engine on %s"
+                             % (type(self).__name__, observations.device, eng.device))
+        batch = DeviceBatch.from_rollout(observations, actions, rewards, done, terminated, steps,
+                                         baseline=self.baseline, reuse=True)
+        out = self._update(batch, None, gamma=gamma, gae_lambda=gae_lambda)
+        self._last_batch = None
+        if fit_baseline and type(self.baseline).__name__ == "LinearBaseline":
+            ts = timer.time()
+            err = eng.fit_linear_baseline(batch, self.baseline, return_errors=self.save_logs)
+            if self.save_logs:
+                self.logger.log_kv("time_VF", timer.time() - ts)
+                self.logger.log_kv("VF_error_before", err[0])
+                self.logger.log_kv("VF_error_after", err[1])
+        return out
+
     # ---- hooks for subclasses ---------------------------------------------------
     def _demo_paths(self):
         return None
@@ -448,10 +502,11 @@ class BatchREINFORCE:
         self.logger.log_kv("surr_improvement", res["surr_after"] - res["surr_before"])
         self.logger.log_kv("running_score", self.running_score)
 
-    def _update(self, batch, paths, skip_gae=False, gamma=0.995):
+    def _update(self, batch, paths, skip_gae=False, gamma=0.995, gae_lambda=None):
+        """paths None (train_from_rollout: there are no host paths): no success rate is logged."""
         eng = self.engine()
         args = self._update_args()
-        res = eng.update(batch, self._theta(), skip_gae=skip_gae, gamma=gamma, gae_lambda=None, **args)
+        res = eng.update(batch, self._theta(), skip_gae=skip_gae, gamma=gamma, gae_lambda=gae_lambda, **args)
         self.last_update = res
         base_stats = [float(v) for v in res["base_stats"]]
         mean_return = base_stats[0]
@@ -464,7 +519,8 @@ class BatchREINFORCE:
             self.logger.log_kv("stoc_pol_max", base_stats[3])
             self.logger.log_kv("stoc_pol_min", base_stats[2])
             self._log_update(res)
-            self._log_success(paths)
+            if paths is not None:
+                self._log_success(paths)
         return base_stats
 
     def _log_success(self, paths):

@@ -200,6 +200,9 @@ class _PinnedStaging:
         # a list to record per-chunk host fill times and device copy events into
         # (bench.py's e2e timeline), or None
         self.trace = None
+        # twice the most paths a DeviceBatch.from_rollout call has cut: how much of
+        # the path table the next call reads back with the counts
+        self.rollout_paths = 0
 
     def pool(self):
         if self._pool is None:
@@ -212,6 +215,14 @@ class _PinnedStaging:
         if st is None:
             st = self._copy[device] = torch.cuda.Stream(device=device)
         return st
+
+    def pinned(self, slot, nbytes):
+        """A grow-only pinned host buffer of `nbytes` bytes (uint8; the caller
+        orders its own copies in and out of it)."""
+        h = self._host.get(slot)
+        if h is None or h.numel() < max(nbytes, 1):
+            h = self._host[slot] = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+        return h[:nbytes]
 
     def device_slot(self, slot, numel, dtype, device):
         """A reused device buffer of `numel` elements (no host data)."""
@@ -597,6 +608,131 @@ class DeviceBatch:
         b.obs_inexact = inexact
         if pre is not None and pre.get("obs_lo") is not None and inexact:
             b._obs_lo = pre["obs_lo"]   # the controller's low halves, copied on first use
+        return b
+
+    @classmethod
+    def from_rollout(cls, observations, actions, rewards, done, terminated=None, steps=None, baseline=None,
+                     reuse=True):
+        """The batch of a step-major rollout that is already in HBM: observations
+        [H][E][n] and actions [H][E][m] (float32 or float64, one dtype), rewards
+        [H][E] (float32 or float64), done [H][E] (uint8 or bool; auto-reset
+        environments: non-zero where env e's episode ended with step t), all
+        C-contiguous torch tensors on one GPU.  terminated [H][E] (or None = done),
+        read only at done cells: whether that end was a true termination
+        (bootstrap 0) or a time limit (bootstrap b[-1], process_samples.py:24-27).
+        steps: host sequence of E valid step counts in [0, H] (None: H each); cells
+        with t >= steps[e] are never read.
+
+        The rollout is cut into paths and laid out path-major on the device
+        (csrc/ingest.hip; the cut is samplers/rollout_ingest.py's, and
+        rollout_to_paths there gives the equivalent host paths): env-ascending,
+        then time-ascending, cut after every done cell, a non-empty remainder a
+        last unterminated path.  Every path is a trajectory of its own (time
+        features restart at 0 in each): a rollout that continues an episode of
+        the previous call is not supported.  Observations / actions keep their
+        dtype, rewards become float64, float32 observations also give obs_range
+        in the same pass.  One host synchronisation: the read of (P, T) and of the
+        path table (batch.lengths); a second one only when P exceeds the table
+        prefix copied with it, which is sized from the calls before.
+        baseline: a LinearBaseline (predictions on the device from the packed
+        rows; zeros before its first fit), a ZeroBaseline or None (zeros); any
+        other class raises ValueError, as its predict needs host paths.
+        reuse: write into the engine-wide grow-only device buffers (one batch
+        alive at a time, stable addresses: no allocation in steady state and
+        hipGraph replay of the update applies)."""
+        H, E, n, m, steps_h, coeffs = cls.check_rollout(observations, actions, rewards, done, terminated, steps,
+                                                        baseline)
+        with torch.cuda.device(observations.device):
+            return cls._from_rollout(observations, actions, rewards, done, terminated, None if steps is None else
+                                     steps_h, coeffs, (H, E, n, m), int(steps_h.sum()), reuse)
+
+    @staticmethod
+    def check_rollout(observations, actions, rewards, done, terminated=None, steps=None, baseline=None):
+        """from_rollout's argument checks (samplers/rollout_ingest.py:check_rollout,
+        then the baseline's class), made without loading the GPU library.  Returns
+        (H, E, n, m, steps as int64 [E], the LinearBaseline's coefficients or
+        None); raises ValueError naming the argument or the class."""
+        from .samplers.rollout_ingest import check_rollout
+        kind = type(baseline).__name__
+        linear = kind == "LinearBaseline" and hasattr(baseline, "_coeffs")
+        if baseline is not None and kind != "ZeroBaseline" and not linear:
+            raise ValueError("from_rollout takes a LinearBaseline, a ZeroBaseline or None, got %s: its predict and "
+                             "fit need host paths (DeviceBatch.from_paths) or streamed feature rows" % kind)
+        H, E, n, m, steps_h = check_rollout(observations, actions, rewards, done, terminated, steps)
+        coeffs = _linear_coeffs(baseline, n) if linear else None
+        if coeffs is False:
+            raise ValueError("from_rollout: the LinearBaseline's %d coefficients do not fit obs_dim %d"
+                             % (len(baseline._coeffs), n))
+        return H, E, n, m, steps_h, coeffs
+
+    @classmethod
+    def _from_rollout(cls, obs, act, rew, done, terminated, steps_h, coeffs, dims, T, reuse):
+        H, E, n, m = dims
+        dev = obs.device
+        K, st = _lib.calls(), _lib.stream_ptr()
+
+        def slot(name, numel, tdt, fresh=False):
+            if fresh:
+                return torch.empty(numel, dtype=tdt, device=dev)
+            nb = numel * torch.empty(0, dtype=tdt).element_size()
+            return _STAGING.device_slot(name, (nb + 7) // 8, np.float64, dev).view(torch.uint8)[:nb].view(tdt)
+
+        out = not reuse   # the batch's own tensors: fresh memory unless the caller reuses the slots
+        o = slot("obs", T * n, obs.dtype, out).view(T, n)
+        a = slot("act", T * m, act.dtype, out).view(T, m)
+        r = slot("rew", T, torch.float64, out)
+        off = slot("off", T + 1, torch.int64, out)
+        term = slot("term", T, torch.uint8, out)
+        env_row = slot("ro_env_row", E + 1, torch.int64)
+        counts = slot("ro_counts", 2, torch.int64)
+        nw = C.c_int64()
+        K.mjrl_rollout_segments_scratch(E, nw)
+        seg = slot("ro_seg", nw.value, torch.int64)
+        steps_d = None
+        if steps_h is not None:
+            # through pinned memory: the copy is stream-ordered and this call's one
+            # synchronisation (below) comes after it, so the next call may rewrite it
+            hs = _STAGING.pinned("ro_steps", 8 * E).view(torch.int64)
+            hs.copy_(torch.from_numpy(steps_h))
+            steps_d = slot("ro_steps", E, torch.int64)
+            steps_d.copy_(hs, non_blocking=True)
+        K.mjrl_rollout_segments(done, terminated, steps_d, H, E, T, env_row, off, term, counts, seg, st)
+        # the one readback: (P, T) and the head of the path table, as many entries as
+        # twice the most paths a call has had (at least two per env)
+        cap = min(T, max(_STAGING.rollout_paths, 2 * E + 64))
+        host = _STAGING.pinned("ro_table", 8 * (cap + 3)).view(torch.int64)
+        host[:2].copy_(counts, non_blocking=True)
+        host[2:3 + cap].copy_(off[:cap + 1], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        orange = None
+        if obs.dtype == torch.float32:
+            nf = C.c_int64()
+            K.mjrl_rollout_pack_scratch(T, n, nf)
+            part = slot("ro_part", nf.value, torch.float32)
+            orange = slot("orange", 2 * n, torch.float32, out).view(2, n)
+        K.mjrl_rollout_pack(obs, act, rew, int(obs.dtype == torch.float64), int(rew.dtype == torch.float64), steps_d,
+                            env_row, H, E, n, m, T, o, a, r, orange, part if orange is not None else None, st)
+        ev.synchronize()
+        P = int(host[0])
+        if int(host[1]) != T or P > T:
+            raise _lib.MjrlError("mjrl_rollout_segments counted %d rows, the steps give %d" % (int(host[1]), T))
+        if P > cap:   # more paths than any call before had: the whole table, a second wait
+            host = _STAGING.pinned("ro_table", 8 * (P + 3)).view(torch.int64)
+            host[2:3 + P].copy_(off[:P + 1], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+        _STAGING.rollout_paths = max(_STAGING.rollout_paths, 2 * P)
+        lengths = np.diff(host[2:3 + P].numpy())
+        off, term = off[:P + 1], term[:P]
+        base = slot("base", T, torch.float64, out)
+        base.zero_()
+        if coeffs is not None and T > 0:
+            # LinearBaseline.predict on the packed rows (as from_paths' device predict)
+            c = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64)).to(dev)
+            fn = K.mjrl_linear_baseline_f32 if o.dtype == torch.float32 else K.mjrl_linear_baseline
+            fn(o, T, n, off, P, c, base, st)
+        b = cls(o, a, r, base, off, term, obs_range=orange)
+        b.lengths = lengths
         return b
 
     def obs_lo(self, paths=None, reuse=True):

@@ -1,0 +1,127 @@
+"""DeviceBatch.from_rollout against DeviceBatch.from_paths on the same samples, at
+the Humanoid shape: E = 1000 environments x H = 1000 steps (1M rows, n = 376,
+m = 17, float32), every environment done every 250 - 1000 steps.
+
+    python tools/rollout_ingest_bench.py [--envs 1000] [--steps 1000] [--n 376] [--m 17] [--alternations 5]
+
+One process times three things: from_rollout on the step-major device tensors,
+from_paths (float32 staging, reused buffers) on the equivalent host paths
+(rollout_ingest.rollout_to_paths, made once, untimed), and the two kernels alone
+(mjrl_rollout_segments, mjrl_rollout_pack; device events).  The runs alternate: a
+warm-up round whose times are dropped, then `--alternations` rounds.  A call is
+timed on the host clock from its start to a device synchronise after it.  Prints
+the medians and ranges as one JSON line, with the pack's share of its floor
+(bytes read plus bytes written over 8 TB/s) and the ratio to from_paths; exits 1
+unless the median of from_rollout is below the minimum of from_paths.  Needs a GPU."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+HBM_BYTES_PER_S = 8e12
+
+
+def summary(xs):
+    return dict(median_ms=1e3 * statistics.median(xs), min_ms=1e3 * min(xs), max_ms=1e3 * max(xs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--n", type=int, default=376)
+    ap.add_argument("--m", type=int, default=17)
+    ap.add_argument("--alternations", type=int, default=5)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from mjrl_amd import _lib
+    from mjrl_amd.engine import DeviceBatch
+    from mjrl_amd.samplers import rollout_ingest as RI
+    H, E, n, m = args.steps, args.envs, args.n, args.m
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    obs = torch.randn((H, E, n), generator=g, device=dev, dtype=torch.float32)
+    act = torch.randn((H, E, m), generator=g, device=dev, dtype=torch.float32)
+    rew = torch.randn((H, E), generator=g, device=dev, dtype=torch.float32)
+    rs = np.random.RandomState(0)
+    done = np.zeros((H, E), np.uint8)
+    for e in range(E):   # an episode of 250 - 1000 steps after another
+        t = -1
+        while True:
+            t += int(rs.randint(min(250, H), min(1000, H) + 1))
+            if t >= H:
+                break
+            done[t, e] = 1
+    d_done = torch.from_numpy(done).to(dev)
+    paths = RI.rollout_to_paths(obs, act, rew, done)
+    T, P = H * E, len(paths)
+
+    def sync_time(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def roll():
+        return DeviceBatch.from_rollout(obs, act, rew, d_done, reuse=True)
+
+    def stage():
+        return DeviceBatch.from_paths(paths, dev, obs_dtype=np.float32, reuse=True)
+
+    # the kernels alone, on buffers of their own
+    K, st = _lib.calls(), _lib.stream_ptr()
+    i64 = dict(dtype=torch.int64, device=dev)
+    nw, nf = C.c_int64(), C.c_int64()
+    K.mjrl_rollout_segments_scratch(E, nw)
+    K.mjrl_rollout_pack_scratch(T, n, nf)
+    env_row, off, counts = torch.zeros(E + 1, **i64), torch.zeros(T + 1, **i64), torch.zeros(2, **i64)
+    term = torch.zeros(T, dtype=torch.uint8, device=dev)
+    seg = torch.zeros(max(nw.value, 1), **i64)
+    o, a = torch.empty((T, n), dtype=torch.float32, device=dev), torch.empty((T, m), dtype=torch.float32, device=dev)
+    r = torch.empty(T, dtype=torch.float64, device=dev)
+    rng, part = torch.empty((2, n), dtype=torch.float32, device=dev), torch.empty(nf.value, dtype=torch.float32, device=dev)
+
+    def kernels():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        K.mjrl_rollout_segments(d_done, None, None, H, E, T, env_row, off, term, counts, seg, st)
+        ev[1].record()
+        K.mjrl_rollout_pack(obs, act, rew, 0, 0, None, env_row, H, E, n, m, T, o, a, r, rng, part, st)
+        ev[2].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / 1e3, ev[1].elapsed_time(ev[2]) / 1e3
+
+    times = dict(from_rollout=[], from_paths=[], segments=[], pack=[])
+    for it in range(args.alternations + 1):   # round 0 warms up
+        tr, b = sync_time(roll)
+        assert (b.T, b.P) == (T, P)
+        tp, b = sync_time(stage)
+        assert (b.T, b.P) == (T, P)
+        ts, tk = kernels()
+        if it:
+            for k, v in (("from_rollout", tr), ("from_paths", tp), ("segments", ts), ("pack", tk)):
+                times[k].append(v)
+    pack_bytes = T * (2 * 4 * (n + m) + 4 + 8)   # rows read and written, f32 reward in, f64 out
+    floor = pack_bytes / HBM_BYTES_PER_S
+    res = {k: summary(v) for k, v in times.items()}
+    res.update(rows=T, paths=P, envs=E, steps=H, n=n, m=m, alternations=args.alternations, pack_bytes=pack_bytes,
+               pack_floor_ms=1e3 * floor, pack_floor_fraction=floor / statistics.median(times["pack"]),
+               ratio_from_paths_over_from_rollout=statistics.median(times["from_paths"]) /
+               statistics.median(times["from_rollout"]))
+    ok = statistics.median(times["from_rollout"]) < min(times["from_paths"])
+    res["from_rollout_median_below_from_paths_min"] = ok
+    print(json.dumps(res))
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
