@@ -165,6 +165,16 @@ int mjrl_gae_scan(const double* rew, const double* base, const int64_t* path_off
                   const uint8_t* terminated, int64_t P, double gamma, double gae_lambda,
                   int32_t use_gae, double* ret, double* adv, double* path_ret, void* stream);
 
+/* The returns of open fragments, bootstrapped (process_samples.py:37-44 with its
+ * terminal argument): for every non-empty path p with terminated[p] == 0, ret over
+ * the path's rows is rewritten as discount_sum(rewards, gamma, terminal = base[last
+ * row of the path]), bit for bit (y_L = terminal, y_t = r_t + gamma y_{t+1}, multiply
+ * then add, no FMA); paths with flag 1 and empty paths are left as they are.  One
+ * wave per path, LDS windows of 1024 steps, the chain state carried across windows.
+ * MJRL_EINVAL for P < 0 or P > 0 with a null array; P == 0 is MJRL_OK without a launch. */
+int mjrl_returns_seeded(const double* rew, const double* base, const int64_t* path_off,
+                        const uint8_t* terminated, int64_t P, double gamma, double* ret, void* stream);
+
 /* ---- LinearBaseline.predict on device (baselines/linear_baseline.py:10-18, 46-49) ----
  * out[t] = [clip(obs_t, +-10), a, a^2, a^3, 1] . coeffs[n+4], a = (t - path start)/1000,
  * for every row of every path (the input of mjrl_gae, process_samples.py:23). */
@@ -174,6 +184,18 @@ int mjrl_linear_baseline(const double* obs, int64_t T, int32_t n, const int64_t*
 /* The same from f32-staged observations (features computed in fp64 from them). */
 int mjrl_linear_baseline_f32(const float* obs, int64_t T, int32_t n, const int64_t* path_off,
                              int64_t P, const double* coeffs, double* out, void* stream);
+
+/* Both with a time origin per path: path_t0 [P] int64 >= 0 (device; null: zeros, the
+ * entries above bit for bit), a = (t - path start + path_t0[p]) / 1000 — the integer
+ * sum first, then one division, (np.arange(L) + t0) / 1000.0 bit for bit.  A path that
+ * continues an episode of the call before (mjrl_rollout_segments_carry) keeps the
+ * episode's clock. */
+int mjrl_linear_baseline_t0(const double* obs, int64_t T, int32_t n, const int64_t* path_off,
+                            const int64_t* path_t0, int64_t P, const double* coeffs, double* out,
+                            void* stream);
+int mjrl_linear_baseline_f32_t0(const float* obs, int64_t T, int32_t n, const int64_t* path_off,
+                                const int64_t* path_t0, int64_t P, const double* coeffs, double* out,
+                                void* stream);
 
 /* ---- LinearBaseline.fit normal equations on device (baselines/linear_baseline.py:20-44) ----
  * Gram matrix of the augmented rows [f_t, y_t], f_t = [clip(obs_t, +-10), a, a^2, a^3, 1]
@@ -197,6 +219,21 @@ int mjrl_linear_baseline_residual(const double* obs, const double* returns, int6
 int mjrl_linear_baseline_residual_f32(const float* obs, const double* returns, int64_t T, int32_t n,
                                       const int64_t* path_off, int64_t P, const double* coeffs,
                                       double* scratch, double* out, void* stream);
+/* The four above with a time origin per path (path_t0 [P] int64, nullable = zeros = the
+ * entries above bit for bit): a = (t - path start + path_t0[p]) / 1000, as
+ * mjrl_linear_baseline_t0. */
+int mjrl_linear_baseline_gram_t0(const double* obs, const double* returns, int64_t T, int32_t n,
+                                 const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                 double* scratch, double* out, void* stream);
+int mjrl_linear_baseline_gram_f32_t0(const float* obs, const double* returns, int64_t T, int32_t n,
+                                     const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                     double* scratch, double* out, void* stream);
+int mjrl_linear_baseline_residual_t0(const double* obs, const double* returns, int64_t T, int32_t n,
+                                     const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                     const double* coeffs, double* scratch, double* out, void* stream);
+int mjrl_linear_baseline_residual_f32_t0(const float* obs, const double* returns, int64_t T, int32_t n,
+                                         const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                         const double* coeffs, double* scratch, double* out, void* stream);
 /* Both from observations staged as an f32 pair, obs = hi + lo (mjrl_host_stage_paths_f64x
  * rows + mjrl_host_stage_lo_paths_f64 low halves): the features are formed in fp64 from
  * (double)hi + (double)lo, i.e. from the sampler's f64 values to 2^-48, so the fit
@@ -558,6 +595,25 @@ int mjrl_rollout_segments_scratch(int64_t E, int64_t* words);
 int mjrl_rollout_segments(const uint8_t* done, const uint8_t* terminated, const int64_t* steps, int64_t H, int64_t E,
                           int64_t path_cap, int64_t* env_row, int64_t* path_off, uint8_t* path_term, int64_t* counts,
                           int64_t* scratch, void* stream);
+/* The same cut for a rollout that continues the episodes of the call before.  The
+ * carry, defined once: episode_steps_in [E] int64 (nullable = zeros; a negative value
+ * is clamped to 0) is c[e], the steps env e's running episode had taken before cell
+ * (0, e).  Beside mjrl_rollout_segments' outputs (the same bits):
+ *   path_t0 [path_cap]: c[e] for env e's path that starts at t = 0, else 0 (the time
+ *     origin of mjrl_linear_baseline*_t0); P entries, nothing at or beyond path_cap;
+ *   env_path [E + 1]: env e's first path, env_path[E] = P (an env without steps has
+ *     env_path[e] == env_path[e + 1]);
+ *   episode_steps_out [E]: the next call's carry — c[e] for an env with no steps, 0
+ *     when its last valid cell is done, else the length of its last path, plus c[e]
+ *     when that path starts at t = 0.  May alias episode_steps_in: each env's lane
+ *     reads its entry before it writes it.
+ * path_t0, env_path and episode_steps_out are each nullable (not written); with all
+ * four null this is mjrl_rollout_segments, which forwards here.  The same three
+ * launches; the MJRL_EINVAL rules are mjrl_rollout_segments'. */
+int mjrl_rollout_segments_carry(const uint8_t* done, const uint8_t* terminated, const int64_t* steps, int64_t H,
+                                int64_t E, int64_t path_cap, const int64_t* episode_steps_in, int64_t* env_row,
+                                int64_t* path_off, uint8_t* path_term, int64_t* path_t0, int64_t* env_path,
+                                int64_t* episode_steps_out, int64_t* counts, int64_t* scratch, void* stream);
 /* The transposing pack: row R[e] + t of obs_out [T][n], act_out [T][m] and rew_out [T]
  * receives obs[t][e][:], act[t][e][:] and rew[t][e], for every valid cell.
  * Observations and actions are f32 (obs_f64 = 0) or f64 (1) and keep their bits;

@@ -102,6 +102,9 @@ SIGNATURES = {
     "mjrl_gae_scan": [P, P, P, P, I64, F64, F64, I32, P, P, P, P],
     "mjrl_linear_baseline": [P, I64, I32, P, I64, P, P, P],
     "mjrl_linear_baseline_f32": [P, I64, I32, P, I64, P, P, P],
+    "mjrl_linear_baseline_t0": [P, I64, I32, P, P, I64, P, P, P],
+    "mjrl_linear_baseline_f32_t0": [P, I64, I32, P, P, I64, P, P, P],
+    "mjrl_returns_seeded": [P, P, P, P, I64, F64, P, P],
     "mjrl_moments": [P, I64, P, P, P, P],
     "mjrl_moments_f32": [P, I64, P, P, P, P],
     "mjrl_moments2": [P, I64, P, P, I64, P, P, P, P, P],
@@ -139,6 +142,10 @@ SIGNATURES = {
     "mjrl_linear_baseline_residual": [P, P, I64, I32, P, I64, P, P, P, P],
     "mjrl_linear_baseline_gram_f32": [P, P, I64, I32, P, I64, P, P, P],
     "mjrl_linear_baseline_residual_f32": [P, P, I64, I32, P, I64, P, P, P, P],
+    "mjrl_linear_baseline_gram_t0": [P, P, I64, I32, P, P, I64, P, P, P],
+    "mjrl_linear_baseline_residual_t0": [P, P, I64, I32, P, P, I64, P, P, P, P],
+    "mjrl_linear_baseline_gram_f32_t0": [P, P, I64, I32, P, P, I64, P, P, P],
+    "mjrl_linear_baseline_residual_f32_t0": [P, P, I64, I32, P, P, I64, P, P, P, P],
     "mjrl_linear_baseline_gram_f32x2": [P, P, P, I64, I32, P, I64, P, P, P],
     "mjrl_linear_baseline_residual_f32x2": [P, P, P, I64, I32, P, I64, P, P, P, P],
     "mjrl_quadratic_baseline_gram_scratch": [I32, I64, C.POINTER(I64)],
@@ -155,6 +162,7 @@ SIGNATURES = {
     "mjrl_value_features_finish_runs": [P, P, I64, I32, I64, I64, I64, P, P, P],
     "mjrl_rollout_segments_scratch": [I64, C.POINTER(I64)],
     "mjrl_rollout_segments": [P, P, P, I64, I64, I64, P, P, P, P, P, P],
+    "mjrl_rollout_segments_carry": [P, P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P],
     "mjrl_rollout_pack_scratch": [I64, I32, C.POINTER(I64)],
     "mjrl_rollout_pack": [P, P, P, I32, I32, P, P, I64, I64, I32, I32, I64, P, P, P, P, P, P],
     "mjrl_value_mlp_scratch": [I32, I32, C.POINTER(I64)],

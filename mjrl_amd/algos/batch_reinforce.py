@@ -119,6 +119,7 @@ class BatchREINFORCE:
         d["_last_batch"] = None   # device tensors
         d.pop("_stream", None)    # pinned slabs / device slots of the streaming sink
         d.pop("_pre", None)       # views of a pool worker's shared segment
+        d.pop("_episodes", None)  # device tensors of the last carried rollout
         if not isinstance(d.get("_comm"), (LocalComm, type(None))):
             d["_comm"] = None     # a process group does not pickle; re-resolved on use
         return d
@@ -425,7 +426,7 @@ class BatchREINFORCE:
         return self._update(batch, paths)
 
     def train_from_rollout(self, observations, actions, rewards, done, terminated=None, steps=None, gamma=0.995,
-                           gae_lambda=0.98, fit_baseline=True):
+                           gae_lambda=0.98, fit_baseline=True, carry=None, bootstrap_returns=False):
         """One update from a step-major rollout that is already in GPU memory
         (a batched simulator, a replay of logged data, another library's sampler):
         observations [H][E][n], actions [H][E][m], rewards [H][E], done [H][E] and
@@ -437,6 +438,18 @@ class BatchREINFORCE:
         fit_baseline) the LinearBaseline fit from the rows and returns still in
         HBM.  Returns [mean, std, min, max] of the path returns.  For the path
         dicts (logging, evaluate_success) see samplers.rollout_ingest.rollout_to_paths.
+        carry: a samplers.rollout_ingest.RolloutCarry kept by the caller across
+        calls, for rollouts that continue the episodes of the call before (auto-reset
+        environments stepped a few dozen steps per update): the LinearBaseline's
+        time features keep each episode's clock in predict and fit, the carry is
+        advanced on the device, and the returns of whole episodes are kept for
+        episode_returns() (with save_logs: episodes_done, episode_return_mean); the
+        returned statistics stay per path.  bootstrap_returns: the fit targets of an
+        unterminated path continue past its cut with its last baseline prediction,
+        discount_sum(rewards, gamma, terminal = b[-1]) (mjrl_returns_seeded, after
+        the update: the update itself reads GAE advantages, which bootstrap
+        already); needs gae_lambda in [0, 1], as plain advantages are returns -
+        baseline with the unbootstrapped returns.
         BatchREINFORCE, NPG and TRPO with a LinearBaseline, a ZeroBaseline or no
         baseline, on one GPU in this process."""
         for k in type(self).__mro__:
@@ -457,7 +470,11 @@ class BatchREINFORCE:
         if world > 1:
             raise ValueError("%s.train_from_rollout: world size %d: sharded runs take host paths (train_step)"
                              % (type(self).__name__, world))
-        DeviceBatch.check_rollout(observations, actions, rewards, done, terminated, steps, self.baseline)
+        if bootstrap_returns and (gae_lambda is None or gae_lambda < 0.0 or gae_lambda > 1.0):
+            raise ValueError("%s.train_from_rollout: bootstrap_returns needs GAE (gae_lambda in [0, 1], got %r): "
+                             "plain advantages are returns - baseline and would read the unbootstrapped returns"
+                             % (type(self).__name__, gae_lambda))
+        DeviceBatch.check_rollout(observations, actions, rewards, done, terminated, steps, self.baseline, carry)
         if self.comm().world_size > 1:   # a process group initialised by the caller
             raise ValueError("%s.train_from_rollout: world size %d: sharded runs take host paths (train_step)"
                              % (type(self).__name__, self.comm().world_size))
@@ -466,9 +483,15 @@ class BatchREINFORCE:
             raise ValueError("%s.train_from_rollout: the rollout is on %s, the agent's engine on %s"
                              % (type(self).__name__, observations.device, eng.device))
         batch = DeviceBatch.from_rollout(observations, actions, rewards, done, terminated, steps,
-                                         baseline=self.baseline, reuse=True)
+                                         baseline=self.baseline, reuse=True, carry=carry)
         out = self._update(batch, None, gamma=gamma, gae_lambda=gae_lambda)
         self._last_batch = None
+        if bootstrap_returns:
+            # outside the (possibly replayed) update graph: the returns in ws["ret"] are
+            # only the baseline fit's targets from here on
+            eng.seed_returns(batch, gamma)
+        if carry is not None:
+            self._episode_statistics(batch, carry)
         if fit_baseline and type(self.baseline).__name__ == "LinearBaseline":
             ts = timer.time()
             err = eng.fit_linear_baseline(batch, self.baseline, return_errors=self.save_logs)
@@ -477,6 +500,46 @@ class BatchREINFORCE:
                 self.logger.log_kv("VF_error_before", err[0])
                 self.logger.log_kv("VF_error_after", err[1])
         return out
+
+    def _episode_statistics(self, batch, carry):
+        """Whole-episode returns of a carried rollout, on the device without a host
+        synchronisation: full[p] = the path's return, plus what its episode had
+        collected before the rollout (carry.episode_return) for an env's first path.
+        A path is closed unless it is its env's last one and the env's episode goes
+        on (carry.episode_steps > 0 after the cut).  carry.episode_return becomes
+        full[last path] for an open tail, 0 after a closed one, and stays for an env
+        without steps."""
+        P = batch.P
+        pr = self.engine().ws["path_ret"][:P]
+        if P == 0:
+            self._episodes = (pr.clone(), torch.zeros(0, dtype=torch.bool, device=pr.device))
+            return
+        first, nxt = batch.env_path[:-1], batch.env_path[1:]
+        has = nxt > first                                   # the env has steps in this rollout
+        zero = torch.zeros_like(carry.episode_return)
+        full = pr.clone()
+        # an env without paths points at its neighbour's path (or past the end): it adds 0
+        full.index_add_(0, first.clamp(max=P - 1), torch.where(has, carry.episode_return, zero))
+        last = (nxt - 1).clamp(min=0, max=P - 1)
+        is_open = has & (carry.episode_steps > 0)
+        closed = torch.zeros(P, dtype=torch.int64, device=pr.device).index_add_(0, last, is_open.to(torch.int64)) == 0
+        carry.episode_return.copy_(torch.where(has, torch.where(is_open, full[last], zero), carry.episode_return))
+        self._episodes = (full, closed)
+        if self.save_logs:
+            done = full[closed]
+            self.logger.log_kv("episodes_done", int(done.numel()))
+            self.logger.log_kv("episode_return_mean", float(done.mean()) if done.numel() else float("nan"))
+
+    def episode_returns(self):
+        """The returns of the episodes that ended in the last train_from_rollout(carry=)
+        call (float64 NumPy, path order): each one's rewards over every rollout it
+        ran through.  The masked select here is the route's one extra host
+        synchronisation, made only when this is called."""
+        ep = getattr(self, "_episodes", None)
+        if ep is None:
+            raise ValueError("%s.episode_returns: no train_from_rollout(carry=) call yet" % type(self).__name__)
+        full, closed = ep
+        return full[closed].cpu().numpy()
 
     # ---- hooks for subclasses ---------------------------------------------------
     def _demo_paths(self):

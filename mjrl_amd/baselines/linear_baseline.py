@@ -9,16 +9,22 @@ predict as k_linear_baseline while the paths are staged (engine.DeviceBatch,
 C-ABI mjrl_linear_baseline), and fit as the fp64 MFMA Gram of [features,
 returns] plus the residual pass (UpdateEngine.fit_linear_baseline, C-ABI
 mjrl_linear_baseline_gram / _residual) followed by this class's lstsq retry loop
-on the (n+5) x (n+5) system (§8f row f1).
+on the (n+5) x (n+5) system (§8f row f1).  A path may carry "t0", the steps its
+episode had taken before the path's first row (rollout_ingest.rollout_to_paths with a
+carry): the time features then start there; the device entries take it as path_t0
+(mjrl_linear_baseline*_t0).
 """
 import numpy as np
 
 
-def time_features(obs, clip=10.0):
+def time_features(obs, t0=0, clip=10.0):
+    """t0: the steps the path's episode had taken before its first row (a path cut
+    from a rollout that continues an episode, samplers/rollout_ingest.py): row i has
+    time (i + t0) / 1000, the row t0 + i of the uncut path bit for bit."""
     o = np.clip(obs, -clip, clip)
     if o.ndim > 2:
         o = o.reshape(o.shape[0], -1)
-    t = (np.arange(o.shape[0]) / 1000.0)[:, None]
+    t = ((np.arange(o.shape[0]) + int(t0)) / 1000.0)[:, None]
     return np.concatenate([o, t, t ** 2, t ** 3, np.ones_like(t)], axis=1)
 
 
@@ -29,7 +35,7 @@ class LinearBaseline:
         self._coeffs = None
 
     def _features(self, path):
-        return time_features(path["observations"])
+        return time_features(path["observations"], path.get("t0", 0))
 
     def predict(self, path):
         if self._coeffs is None:

@@ -43,14 +43,16 @@ constexpr int GLD = GT + 16;    // LDS row stride (doubles): rows 1 apart land 3
 constexpr int GSLICES = 24;     // row slices (multiple of 8: one XCD per slice group)
 constexpr int GTHREADS = 256;
 
-// a_t = (t - path start) / 1000 for every row (np.arange(l) / 1000.0); one wave per path
-__global__ void __launch_bounds__(256) k_path_time(const int64_t* __restrict__ off, int64_t P,
+// a_t = (t - path start + t0[p]) / 1000 for every row ((np.arange(l) + t0) / 1000.0: the
+// integer sum first, then the one division); t0 null: zeros.  One wave per path
+__global__ void __launch_bounds__(256) k_path_time(const int64_t* __restrict__ off,
+                                                   const int64_t* __restrict__ t0, int64_t P,
                                                    double* __restrict__ al) {
     const int lane = threadIdx.x & 63;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; p < P; p += nw) {
-        const int64_t b = off[p], e = off[p + 1];
-        for (int64_t t = b + lane; t < e; t += 64) al[t] = (double)(t - b) / 1000.0;
+        const int64_t b = off[p], e = off[p + 1], c = t0 ? t0[p] : 0;
+        for (int64_t t = b + lane; t < e; t += 64) al[t] = (double)(t - b + c) / 1000.0;
     }
 }
 
@@ -350,7 +352,8 @@ int mjrl_linear_baseline_gram_scratch(int32_t n, int64_t T, int64_t* doubles) {
 extern "C++" {
 template <typename TO, bool QUAD = false>
 static int linear_baseline_gram(const TO* obs, const float* lo, const double* returns, int64_t T, int32_t n,
-                                const int64_t* path_off, int64_t P, double* scratch, double* out, void* stream) {
+                                const int64_t* path_off, const int64_t* path_t0, int64_t P, double* scratch,
+                                double* out, void* stream) {
     if (n <= 0 || T < 0 || P < 0 || !out || !scratch || (T > 0 && (!obs || !returns || !path_off)) ||
         (QUAD && n > QMAX_N))
         return MJRL_EINVAL;
@@ -361,7 +364,8 @@ static int linear_baseline_gram(const TO* obs, const float* lo, const double* re
     double* al = scratch + (int64_t)GSLICES * npair * GT * GT;
     if (P > 0) {
         const int64_t g = (P + 3) / 4;
-        hipLaunchKernelGGL(k_path_time, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, st, path_off, P, al);
+        hipLaunchKernelGGL(k_path_time, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, st, path_off, path_t0,
+                           P, al);
     }
     const int groups = (GSLICES + 7) / 8;   // slices per XCD
     if (QUAD) {
@@ -387,8 +391,8 @@ static int linear_baseline_gram(const TO* obs, const float* lo, const double* re
 extern "C++" {
 template <typename TO, bool QUAD = false>
 static int linear_baseline_residual(const TO* obs, const float* lo, const double* returns, int64_t T, int32_t n,
-                                    const int64_t* path_off, int64_t P, const double* coeffs, double* scratch,
-                                    double* out, void* stream) {
+                                    const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                    const double* coeffs, double* scratch, double* out, void* stream) {
     if (n <= 0 || T < 0 || P < 0 || (T > 0 && (!obs || !returns || !path_off || !coeffs || !scratch || !out)) ||
         (QUAD && n > QMAX_N))
         return MJRL_EINVAL;
@@ -399,7 +403,8 @@ static int linear_baseline_residual(const TO* obs, const float* lo, const double
     double* al = scratch + (int64_t)GSLICES * npair * GT * GT;
     if (P > 0) {
         const int64_t g = (P + 3) / 4;
-        hipLaunchKernelGGL(k_path_time, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, st, path_off, P, al);
+        hipLaunchKernelGGL(k_path_time, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, st, path_off, path_t0,
+                           P, al);
     }
     const int64_t g = (T + 3) / 4;
     if (QUAD) {
@@ -415,42 +420,71 @@ static int linear_baseline_residual(const TO* obs, const float* lo, const double
 }
 }  // extern "C++"
 
+// The _t0 forms: path_t0 [P] (nullable: zeros) is each path's time origin, a = (t - path
+// start + path_t0[p]) / 1000; the forms without it forward here with null.
+int mjrl_linear_baseline_gram_t0(const double* obs, const double* returns, int64_t T, int32_t n,
+                                 const int64_t* path_off, const int64_t* path_t0, int64_t P, double* scratch,
+                                 double* out, void* stream) {
+    return linear_baseline_gram(obs, (const float*)nullptr, returns, T, n, path_off, path_t0, P, scratch, out,
+                                stream);
+}
+
+int mjrl_linear_baseline_gram_f32_t0(const float* obs, const double* returns, int64_t T, int32_t n,
+                                     const int64_t* path_off, const int64_t* path_t0, int64_t P, double* scratch,
+                                     double* out, void* stream) {
+    return linear_baseline_gram(obs, (const float*)nullptr, returns, T, n, path_off, path_t0, P, scratch, out,
+                                stream);
+}
+
+int mjrl_linear_baseline_residual_t0(const double* obs, const double* returns, int64_t T, int32_t n,
+                                     const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                     const double* coeffs, double* scratch, double* out, void* stream) {
+    return linear_baseline_residual(obs, (const float*)nullptr, returns, T, n, path_off, path_t0, P, coeffs, scratch,
+                                    out, stream);
+}
+
+int mjrl_linear_baseline_residual_f32_t0(const float* obs, const double* returns, int64_t T, int32_t n,
+                                         const int64_t* path_off, const int64_t* path_t0, int64_t P,
+                                         const double* coeffs, double* scratch, double* out, void* stream) {
+    return linear_baseline_residual(obs, (const float*)nullptr, returns, T, n, path_off, path_t0, P, coeffs, scratch,
+                                    out, stream);
+}
+
 int mjrl_linear_baseline_gram(const double* obs, const double* returns, int64_t T, int32_t n,
                               const int64_t* path_off, int64_t P, double* scratch, double* out, void* stream) {
-    return linear_baseline_gram(obs, (const float*)nullptr, returns, T, n, path_off, P, scratch, out, stream);
+    return mjrl_linear_baseline_gram_t0(obs, returns, T, n, path_off, nullptr, P, scratch, out, stream);
 }
 
 int mjrl_linear_baseline_gram_f32(const float* obs, const double* returns, int64_t T, int32_t n,
                                   const int64_t* path_off, int64_t P, double* scratch, double* out, void* stream) {
-    return linear_baseline_gram(obs, (const float*)nullptr, returns, T, n, path_off, P, scratch, out, stream);
+    return mjrl_linear_baseline_gram_f32_t0(obs, returns, T, n, path_off, nullptr, P, scratch, out, stream);
 }
 
 int mjrl_linear_baseline_residual(const double* obs, const double* returns, int64_t T, int32_t n,
                                   const int64_t* path_off, int64_t P, const double* coeffs, double* scratch,
                                   double* out, void* stream) {
-    return linear_baseline_residual(obs, (const float*)nullptr, returns, T, n, path_off, P, coeffs, scratch, out,
-                                    stream);
+    return mjrl_linear_baseline_residual_t0(obs, returns, T, n, path_off, nullptr, P, coeffs, scratch, out, stream);
 }
 
 int mjrl_linear_baseline_residual_f32(const float* obs, const double* returns, int64_t T, int32_t n,
                                       const int64_t* path_off, int64_t P, const double* coeffs, double* scratch,
                                       double* out, void* stream) {
-    return linear_baseline_residual(obs, (const float*)nullptr, returns, T, n, path_off, P, coeffs, scratch, out,
-                                    stream);
+    return mjrl_linear_baseline_residual_f32_t0(obs, returns, T, n, path_off, nullptr, P, coeffs, scratch, out,
+                                                stream);
 }
 
 int mjrl_linear_baseline_gram_f32x2(const float* obs, const float* obs_lo, const double* returns, int64_t T,
                                     int32_t n, const int64_t* path_off, int64_t P, double* scratch, double* out,
                                     void* stream) {
     if (T > 0 && !obs_lo) return MJRL_EINVAL;
-    return linear_baseline_gram(obs, obs_lo, returns, T, n, path_off, P, scratch, out, stream);
+    return linear_baseline_gram(obs, obs_lo, returns, T, n, path_off, nullptr, P, scratch, out, stream);
 }
 
 int mjrl_linear_baseline_residual_f32x2(const float* obs, const float* obs_lo, const double* returns, int64_t T,
                                         int32_t n, const int64_t* path_off, int64_t P, const double* coeffs,
                                         double* scratch, double* out, void* stream) {
     if (T > 0 && !obs_lo) return MJRL_EINVAL;
-    return linear_baseline_residual(obs, obs_lo, returns, T, n, path_off, P, coeffs, scratch, out, stream);
+    return linear_baseline_residual(obs, obs_lo, returns, T, n, path_off, nullptr, P, coeffs, scratch, out, stream);
 }
 
 int mjrl_quadratic_baseline_gram_scratch(int32_t n, int64_t T, int64_t* doubles) {
@@ -463,26 +497,26 @@ int mjrl_quadratic_baseline_gram_scratch(int32_t n, int64_t T, int64_t* doubles)
 
 int mjrl_quadratic_baseline_gram(const double* obs, const double* returns, int64_t T, int32_t n,
                                  const int64_t* path_off, int64_t P, double* scratch, double* out, void* stream) {
-    return linear_baseline_gram<double, true>(obs, nullptr, returns, T, n, path_off, P, scratch, out, stream);
+    return linear_baseline_gram<double, true>(obs, nullptr, returns, T, n, path_off, nullptr, P, scratch, out, stream);
 }
 
 int mjrl_quadratic_baseline_gram_f32(const float* obs, const float* obs_lo, const double* returns, int64_t T,
                                      int32_t n, const int64_t* path_off, int64_t P, double* scratch, double* out,
                                      void* stream) {
-    return linear_baseline_gram<float, true>(obs, obs_lo, returns, T, n, path_off, P, scratch, out, stream);
+    return linear_baseline_gram<float, true>(obs, obs_lo, returns, T, n, path_off, nullptr, P, scratch, out, stream);
 }
 
 int mjrl_quadratic_baseline_residual(const double* obs, const double* returns, int64_t T, int32_t n,
                                      const int64_t* path_off, int64_t P, const double* coeffs, double* scratch,
                                      double* out, void* stream) {
-    return linear_baseline_residual<double, true>(obs, nullptr, returns, T, n, path_off, P, coeffs, scratch, out,
+    return linear_baseline_residual<double, true>(obs, nullptr, returns, T, n, path_off, nullptr, P, coeffs, scratch, out,
                                                   stream);
 }
 
 int mjrl_quadratic_baseline_residual_f32(const float* obs, const float* obs_lo, const double* returns, int64_t T,
                                          int32_t n, const int64_t* path_off, int64_t P, const double* coeffs,
                                          double* scratch, double* out, void* stream) {
-    return linear_baseline_residual<float, true>(obs, obs_lo, returns, T, n, path_off, P, coeffs, scratch, out,
+    return linear_baseline_residual<float, true>(obs, obs_lo, returns, T, n, path_off, nullptr, P, coeffs, scratch, out,
                                                  stream);
 }
 

@@ -534,6 +534,62 @@ __global__ void __launch_bounds__(64 * GAE_WAVES) k_gae(const double* __restrict
     }
 }
 
+// The returns of an open fragment, bootstrapped: for every non-empty path with flag 0,
+// ret = discount_sum(rewards, gamma, terminal = base[last row]) (process_samples.py:
+// 37-44 with its terminal argument; GAE's b1[-1] = b[-1] convention, :24-27).  k_gae's
+// returns chain with a non-zero seed: one wave per path, windows of GW steps walked
+// from the path's end, the rewards into LDS with coalesced loads, lane 0 runs y = r +
+// gamma y out of LDS (__dmul_rn / __dadd_rn: no contraction, bit-identical to the
+// reference's loop) with the chain state carried across windows, the wave stores the
+// window with coalesced writes.  Paths with flag 1 and empty paths are not touched.
+__global__ void __launch_bounds__(64 * GAE_WAVES) k_returns_seeded(const double* __restrict__ rew,
+                                                                   const double* __restrict__ base,
+                                                                   const int64_t* __restrict__ off,
+                                                                   const uint8_t* __restrict__ term, int64_t P,
+                                                                   double gamma, double* __restrict__ ret) {
+    __shared__ double sr[GAE_WAVES][GW];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double* R = sr[w];
+    for (int64_t p = (int64_t)blockIdx.x * GAE_WAVES + w; p < P; p += (int64_t)gridDim.x * GAE_WAVES) {
+        const int64_t b = off[p], e = off[p + 1];
+        if (e <= b || term[p]) continue;   // wave-uniform
+        double acc = base[e - 1];          // y_L, the seed
+        for (int64_t w1 = e; w1 > b; w1 -= GW) {
+            const int64_t w0 = w1 - GW > b ? w1 - GW : b;
+            const int cnt = (int)(w1 - w0);
+            {
+                double x[GW / 64];   // all of the lane's loads in flight at once
+#pragma unroll
+                for (int k = 0; k < GW / 64; ++k) x[k] = lane + 64 * k < cnt ? rew[w0 + lane + 64 * k] : 0.0;
+#pragma unroll
+                for (int k = 0; k < GW / 64; ++k)
+                    if (lane + 64 * k < cnt) R[lane + 64 * k] = x[k];
+            }
+            wave_sync();
+            if (lane == 0) {
+                int i = cnt;
+                for (; i >= GU; i -= GU) {   // steps i-1 .. i-GU
+                    double r[GU];
+#pragma unroll
+                    for (int u = 0; u < GU; ++u) r[u] = R[i - 1 - u];
+#pragma unroll
+                    for (int u = 0; u < GU; ++u) {
+                        acc = __dadd_rn(r[u], __dmul_rn(gamma, acc));
+                        R[i - 1 - u] = acc;
+                    }
+                }
+                for (; i > 0; --i) {
+                    acc = __dadd_rn(R[i - 1], __dmul_rn(gamma, acc));
+                    R[i - 1] = acc;
+                }
+            }
+            wave_sync();
+            for (int i = lane; i < cnt; i += 64) ret[w0 + i] = R[i];
+            wave_sync();
+        }
+    }
+}
+
 // Lanes = paths (round 6): the serial recurrences of LP_PATHS paths run side by side
 // in ONE instruction stream each, one wave per chain, each lane one path — wave 0
 // the returns (discount_sum(rewards, gamma)), wave 1 the advantages (discount_sum(td,
@@ -1049,12 +1105,14 @@ __global__ void __launch_bounds__(256) k_dapg_adv(const double* __restrict__ w64
 
 // LinearBaseline.predict for every path (baselines/linear_baseline.py:10-18,46-49):
 // b_t = clip(o_t, -10, 10) . c[0:n] + (t/1000) c[n] + (t/1000)^2 c[n+1]
-//       + (t/1000)^3 c[n+2] + c[n+3], t = index within the path.
+//       + (t/1000)^3 c[n+2] + c[n+3], t = index within the path + the path's time
+// origin t0[p] (a path that continues an episode of the call before; null: 0).
 // One wave per row (lanes across the observation, coalesced f64 loads), a
 // grid-stride over rows; the row's path comes from a binary search of path_off.
 template <typename TO>
 __global__ void __launch_bounds__(256) k_linear_baseline(const TO* __restrict__ obs, int64_t T, int n,
-                                                         const int64_t* __restrict__ off, int64_t P,
+                                                         const int64_t* __restrict__ off,
+                                                         const int64_t* __restrict__ t0, int64_t P,
                                                          const double* __restrict__ coef, double* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1073,7 +1131,9 @@ __global__ void __launch_bounds__(256) k_linear_baseline(const TO* __restrict__ 
                 const int64_t mid = (lo + hi) >> 1;
                 if (off[mid] <= row) lo = mid; else hi = mid;
             }
-            const double al = (double)(row - off[lo]) / 1000.0;
+            // the path's time origin (t0 null: 0) joins the integer step first, then the
+            // one division: (np.arange(L) + t0) / 1000.0 bit for bit
+            const double al = (double)(row - off[lo] + (t0 ? t0[lo] : 0)) / 1000.0;
             acc += al * coef[n] + (al * al) * coef[n + 1] + pow(al, 3.0) * coef[n + 2] + coef[n + 3];
             out[row] = acc;
         }
@@ -1523,6 +1583,16 @@ int mjrl_gae_wave(const double* rew, const double* base, const int64_t* path_off
     return err(hipGetLastError());
 }
 
+int mjrl_returns_seeded(const double* rew, const double* base, const int64_t* path_off, const uint8_t* terminated,
+                        int64_t P, double gamma, double* ret, void* stream) {
+    if (P < 0 || (P > 0 && (!rew || !base || !path_off || !terminated || !ret))) return MJRL_EINVAL;
+    if (P == 0) return MJRL_OK;
+    const int64_t g = (P + GAE_WAVES - 1) / GAE_WAVES;
+    hipLaunchKernelGGL(k_returns_seeded, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(64 * GAE_WAVES), 0,
+                       (hipStream_t)stream, rew, base, path_off, terminated, P, gamma, ret);
+    return err(hipGetLastError());
+}
+
 static int moments_impl(bool f32, const void* x, int64_t N, const double* center, double* rpart, double* out,
                         void* stream) {
     if (N < 0 || !rpart || !out || (N > 0 && !x)) return MJRL_EINVAL;
@@ -1584,25 +1654,35 @@ int mjrl_dapg_adv(const double* w64, int64_t T, const double* mw1, const double*
 
 extern "C++" {
 template <typename TO>
-static int linear_baseline(const TO* obs, int64_t T, int32_t n, const int64_t* path_off, int64_t P,
-                           const double* coeffs, double* out, void* stream) {
+static int linear_baseline(const TO* obs, int64_t T, int32_t n, const int64_t* path_off, const int64_t* path_t0,
+                           int64_t P, const double* coeffs, double* out, void* stream) {
     if (T < 0 || n <= 0 || P < 0 || (T > 0 && (!obs || !path_off || !coeffs || !out))) return MJRL_EINVAL;
     if (T == 0) return MJRL_OK;
     const int g = grid_for(T * 64, 256, 4096);
-    hipLaunchKernelGGL(k_linear_baseline<TO>, dim3(g), dim3(256), 0, (hipStream_t)stream, obs, T, n, path_off, P,
-                       coeffs, out);
+    hipLaunchKernelGGL(k_linear_baseline<TO>, dim3(g), dim3(256), 0, (hipStream_t)stream, obs, T, n, path_off,
+                       path_t0, P, coeffs, out);
     return err(hipGetLastError());
 }
 }  // extern "C++"
 
+int mjrl_linear_baseline_t0(const double* obs, int64_t T, int32_t n, const int64_t* path_off,
+                            const int64_t* path_t0, int64_t P, const double* coeffs, double* out, void* stream) {
+    return linear_baseline(obs, T, n, path_off, path_t0, P, coeffs, out, stream);
+}
+
+int mjrl_linear_baseline_f32_t0(const float* obs, int64_t T, int32_t n, const int64_t* path_off,
+                                const int64_t* path_t0, int64_t P, const double* coeffs, double* out, void* stream) {
+    return linear_baseline(obs, T, n, path_off, path_t0, P, coeffs, out, stream);
+}
+
 int mjrl_linear_baseline(const double* obs, int64_t T, int32_t n, const int64_t* path_off, int64_t P,
                          const double* coeffs, double* out, void* stream) {
-    return linear_baseline(obs, T, n, path_off, P, coeffs, out, stream);
+    return mjrl_linear_baseline_t0(obs, T, n, path_off, nullptr, P, coeffs, out, stream);
 }
 
 int mjrl_linear_baseline_f32(const float* obs, int64_t T, int32_t n, const int64_t* path_off, int64_t P,
                              const double* coeffs, double* out, void* stream) {
-    return linear_baseline(obs, T, n, path_off, P, coeffs, out, stream);
+    return mjrl_linear_baseline_f32_t0(obs, T, n, path_off, nullptr, P, coeffs, out, stream);
 }
 
 int mjrl_gather_rows(const void* src, int64_t row_bytes, const int64_t* idx, int64_t n, void* dst, void* stream) {

@@ -16,6 +16,14 @@
 //   env-ascending, then time-ascending, so the row of cell (t, e) is R[e] + t, R the
 //   exclusive prefix sum of steps.
 //
+// The carry (mjrl_rollout_segments_carry): c[e] >= 0 steps env e's running episode had
+// taken before cell (0, e).  path_t0[p] = c[e] for env e's path that starts at t = 0,
+// else 0: the time origin of the baselines' time features.  env_path[e] is env e's
+// first path (env_path[E] = P).  c_next[e], the carry of the next call: c[e] for an
+// env with no steps, 0 when its last valid cell is done, else the length of its last
+// path (plus c[e] when that path starts at t = 0).  The extra values ride in the same
+// three launches.
+//
 // mjrl_rollout_segments: latency-bound and tiny (three launches: count, scan, write).
 // mjrl_rollout_pack: HBM-bound, one wave per destination row.  No atomics anywhere:
 // the prefix sums and the column ranges are reduced in one fixed order.
@@ -80,7 +88,8 @@ __global__ void __launch_bounds__(SEG_THREADS) k_seg_scan(const int64_t* __restr
                                                           const int64_t* __restrict__ nrows, int64_t E,
                                                           int64_t path_cap, int64_t* __restrict__ path_base,
                                                           int64_t* __restrict__ env_row, int64_t* __restrict__ path_off,
-                                                          int64_t* __restrict__ counts) {
+                                                          int64_t* __restrict__ counts,
+                                                          int64_t* __restrict__ env_path) {
     __shared__ int64_t sp[SEG_THREADS], sr[SEG_THREADS];
     const int tid = threadIdx.x;
     int64_t cp = 0, cr = 0;   // totals of the chunks before this one (the same in every thread)
@@ -100,6 +109,7 @@ __global__ void __launch_bounds__(SEG_THREADS) k_seg_scan(const int64_t* __restr
         if (e < E) {
             path_base[e] = cp + sp[tid] - vp;
             env_row[e] = cr + sr[tid] - vr;
+            if (env_path) env_path[e] = cp + sp[tid] - vp;
         }
         cp += sp[SEG_THREADS - 1];
         cr += sr[SEG_THREADS - 1];
@@ -110,22 +120,30 @@ __global__ void __launch_bounds__(SEG_THREADS) k_seg_scan(const int64_t* __restr
         counts[0] = cp;
         counts[1] = cr;
         if (cp <= path_cap) path_off[cp] = cr;
+        if (env_path) env_path[E] = cp;
     }
 }
 
 // Phase 3.  One lane per env walks again and writes its paths' first rows and flags
-// from its base; nothing at or beyond path_cap is written.
+// from its base; nothing at or beyond path_cap is written.  With a carry: the time
+// origin of each path (path_t0, nullable) and the env's next carry (carry_out,
+// nullable).  carry_out may be carry_in: the lane reads its entry before it writes it,
+// and no other lane touches it (neither pointer is __restrict__).
 __global__ void __launch_bounds__(SEG_THREADS) k_seg_write(const uint8_t* __restrict__ done,
                                                            const uint8_t* __restrict__ terminated,
                                                            const int64_t* __restrict__ steps, int64_t H, int64_t E,
                                                            int64_t path_cap, const int64_t* __restrict__ path_base,
                                                            const int64_t* __restrict__ env_row,
                                                            int64_t* __restrict__ path_off,
-                                                           uint8_t* __restrict__ path_term) {
+                                                           uint8_t* __restrict__ path_term,
+                                                           const int64_t* carry_in, int64_t* __restrict__ path_t0,
+                                                           int64_t* carry_out) {
     const int64_t e = (int64_t)blockIdx.x * SEG_THREADS + threadIdx.x;
     if (e >= E) return;
     const int64_t s = valid_steps(steps, e, H);
     const int64_t r0 = env_row[e];
+    int64_t c = carry_in ? carry_in[e] : 0;
+    c = c < 0 ? 0 : c;   // device data: clamped as the steps are
     int64_t p = path_base[e], start = 0;
     for (int64_t t0 = 0; t0 < s; t0 += SEG_UNROLL) {
         uint8_t d[SEG_UNROLL];
@@ -137,6 +155,7 @@ __global__ void __launch_bounds__(SEG_THREADS) k_seg_write(const uint8_t* __rest
                 if (p >= 0 && p < path_cap) {
                     path_off[p] = r0 + start;
                     path_term[p] = terminated ? (uint8_t)(terminated[t * E + e] != 0) : (uint8_t)1;
+                    if (path_t0) path_t0[p] = start == 0 ? c : 0;
                 }
                 ++p;
                 start = t + 1;
@@ -145,7 +164,10 @@ __global__ void __launch_bounds__(SEG_THREADS) k_seg_write(const uint8_t* __rest
     if (start < s && p >= 0 && p < path_cap) {
         path_off[p] = r0 + start;
         path_term[p] = 0;
+        if (path_t0) path_t0[p] = start == 0 ? c : 0;
     }
+    // start is now the first step of the env's last path, or s when its last cell is done
+    if (carry_out) carry_out[e] = s == 0 ? c : (start >= s ? 0 : (s - start) + (start == 0 ? c : 0));
 }
 
 // ---- the transposing pack ----
@@ -312,9 +334,10 @@ int mjrl_rollout_segments_scratch(int64_t E, int64_t* words) {
     return MJRL_OK;
 }
 
-int mjrl_rollout_segments(const uint8_t* done, const uint8_t* terminated, const int64_t* steps, int64_t H, int64_t E,
-                          int64_t path_cap, int64_t* env_row, int64_t* path_off, uint8_t* path_term, int64_t* counts,
-                          int64_t* scratch, void* stream) {
+int mjrl_rollout_segments_carry(const uint8_t* done, const uint8_t* terminated, const int64_t* steps, int64_t H,
+                                int64_t E, int64_t path_cap, const int64_t* episode_steps_in, int64_t* env_row,
+                                int64_t* path_off, uint8_t* path_term, int64_t* path_t0, int64_t* env_path,
+                                int64_t* episode_steps_out, int64_t* counts, int64_t* scratch, void* stream) {
     if (H < 0 || E < 0 || path_cap < 0 || !env_row || !path_off || !counts) return MJRL_EINVAL;
     if (E > 0 && (!scratch || (H > 0 && !done))) return MJRL_EINVAL;
     if (path_cap > 0 && !path_term) return MJRL_EINVAL;
@@ -325,11 +348,18 @@ int mjrl_rollout_segments(const uint8_t* done, const uint8_t* terminated, const 
     const unsigned g = (unsigned)((E + SEG_THREADS - 1) / SEG_THREADS);
     if (g) hipLaunchKernelGGL(k_seg_count, dim3(g), dim3(SEG_THREADS), 0, st, done, steps, H, E, npaths, nrows);
     hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(SEG_THREADS), 0, st, npaths, nrows, E, path_cap, path_base, env_row,
-                       path_off, counts);
+                       path_off, counts, env_path);
     if (g)
         hipLaunchKernelGGL(k_seg_write, dim3(g), dim3(SEG_THREADS), 0, st, done, terminated, steps, H, E, path_cap,
-                           path_base, env_row, path_off, path_term);
+                           path_base, env_row, path_off, path_term, episode_steps_in, path_t0, episode_steps_out);
     return (int)hipGetLastError();
+}
+
+int mjrl_rollout_segments(const uint8_t* done, const uint8_t* terminated, const int64_t* steps, int64_t H, int64_t E,
+                          int64_t path_cap, int64_t* env_row, int64_t* path_off, uint8_t* path_term, int64_t* counts,
+                          int64_t* scratch, void* stream) {
+    return mjrl_rollout_segments_carry(done, terminated, steps, H, E, path_cap, nullptr, env_row, path_off, path_term,
+                                       nullptr, nullptr, nullptr, counts, scratch, stream);
 }
 
 int mjrl_rollout_pack_scratch(int64_t T, int32_t n, int64_t* floats) {

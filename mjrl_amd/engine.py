@@ -483,7 +483,10 @@ class DeviceBatch:
     obs / act: f64 [T_all][n] / [T_all][m], the T RL rows (path order) followed by
     T_demo demonstration rows (DAPG).  rewards, baseline: f64 [T].  path_off:
     i64 [P+1] row offsets; terminated: u8 [P].  advantages (optional, f64 [T]):
-    when given, the GAE scan is skipped (train_from_paths semantics)."""
+    when given, the GAE scan is skipped (train_from_paths semantics).  path_t0
+    (i64 [P]) and env_path (i64 [E + 1]) are set by from_rollout(carry=): each
+    path's time origin (the steps its episode had taken before the rollout, 0 for a
+    path that starts inside it) and each env's first path; None otherwise."""
 
     def __init__(self, obs, act, rewards, baseline, path_off, terminated, advantages=None, T_demo=0, obs_range=None):
         self.obs, self.act = obs, act
@@ -494,6 +497,7 @@ class DeviceBatch:
         self.T_global = None   # all-rank row count, cached by a sharded update
         self.rewards, self.baseline = rewards, baseline
         self.path_off, self.terminated = path_off, terminated
+        self.path_t0 = self.env_path = None
         self.advantages = advantages
         # True when obs holds float32 images of values that are not all float32s
         # (set by from_paths; the device LinearBaseline fit then reads obs_lo too)
@@ -521,7 +525,13 @@ class DeviceBatch:
         already concatenated in obs_dtype in (registered) host memory, with their
         column ranges: copied as they are (a pool worker's shared segment).
         Baseline predictions of other baselines come from the caller's baseline
-        object, per path, as compute_advantages does (process_samples.py:23)."""
+        object, per path, as compute_advantages does (process_samples.py:23).
+        A path with a non-zero "t0" (rollout_ingest.rollout_to_paths with a carry)
+        raises ValueError: host staging has no time origin."""
+        if any(p.get("t0", 0) for p in paths):
+            raise ValueError("DeviceBatch.from_paths: a path carries a non-zero \"t0\" (a rollout cut with a carry): "
+                             "host staging has no time origin, its LinearBaseline predictions and fit would "
+                             "restart the clock; use DeviceBatch.from_rollout(carry=)")
         with torch.cuda.device(device):
             return cls._from_paths(paths, device, baseline, use_advantages, demo_paths, np.dtype(obs_dtype), reuse,
                                    pre)
@@ -612,7 +622,7 @@ class DeviceBatch:
 
     @classmethod
     def from_rollout(cls, observations, actions, rewards, done, terminated=None, steps=None, baseline=None,
-                     reuse=True):
+                     reuse=True, carry=None):
         """The batch of a step-major rollout that is already in HBM: observations
         [H][E][n] and actions [H][E][m] (float32 or float64, one dtype), rewards
         [H][E] (float32 or float64), done [H][E] (uint8 or bool; auto-reset
@@ -627,9 +637,15 @@ class DeviceBatch:
         (csrc/ingest.hip; the cut is samplers/rollout_ingest.py's, and
         rollout_to_paths there gives the equivalent host paths): env-ascending,
         then time-ascending, cut after every done cell, a non-empty remainder a
-        last unterminated path.  Every path is a trajectory of its own (time
-        features restart at 0 in each): a rollout that continues an episode of
-        the previous call is not supported.  Observations / actions keep their
+        last unterminated path.  Without a carry every path is a trajectory of its
+        own (time features restart at 0 in each).  carry: a
+        samplers.rollout_ingest.RolloutCarry of E envs on the rollout's device, for
+        a rollout that continues the episodes of the call before: env e's path that
+        starts at t = 0 keeps the clock of its episode (batch.path_t0, read by the
+        LinearBaseline predict here and by fit_linear_baseline), batch.env_path is
+        each env's first path, and carry.episode_steps is updated in place by the
+        same launches, stream-ordered: no further synchronisation or allocation.
+        Observations / actions keep their
         dtype, rewards become float64, float32 observations also give obs_range
         in the same pass.  One host synchronisation: the read of (P, T) and of the
         path table (batch.lengths); a second one only when P exceeds the table
@@ -641,15 +657,16 @@ class DeviceBatch:
         alive at a time, stable addresses: no allocation in steady state and
         hipGraph replay of the update applies)."""
         H, E, n, m, steps_h, coeffs = cls.check_rollout(observations, actions, rewards, done, terminated, steps,
-                                                        baseline)
+                                                        baseline, carry)
         with torch.cuda.device(observations.device):
             return cls._from_rollout(observations, actions, rewards, done, terminated, None if steps is None else
-                                     steps_h, coeffs, (H, E, n, m), int(steps_h.sum()), reuse)
+                                     steps_h, coeffs, (H, E, n, m), int(steps_h.sum()), reuse, carry)
 
     @staticmethod
-    def check_rollout(observations, actions, rewards, done, terminated=None, steps=None, baseline=None):
+    def check_rollout(observations, actions, rewards, done, terminated=None, steps=None, baseline=None, carry=None):
         """from_rollout's argument checks (samplers/rollout_ingest.py:check_rollout,
-        then the baseline's class), made without loading the GPU library.  Returns
+        the carry among them, then the baseline's class), made without loading the
+        GPU library.  Returns
         (H, E, n, m, steps as int64 [E], the LinearBaseline's coefficients or
         None); raises ValueError naming the argument or the class."""
         from .samplers.rollout_ingest import check_rollout
@@ -658,7 +675,7 @@ class DeviceBatch:
         if baseline is not None and kind != "ZeroBaseline" and not linear:
             raise ValueError("from_rollout takes a LinearBaseline, a ZeroBaseline or None, got %s: its predict and "
                              "fit need host paths (DeviceBatch.from_paths) or streamed feature rows" % kind)
-        H, E, n, m, steps_h = check_rollout(observations, actions, rewards, done, terminated, steps)
+        H, E, n, m, steps_h = check_rollout(observations, actions, rewards, done, terminated, steps, carry)
         coeffs = _linear_coeffs(baseline, n) if linear else None
         if coeffs is False:
             raise ValueError("from_rollout: the LinearBaseline's %d coefficients do not fit obs_dim %d"
@@ -666,7 +683,7 @@ class DeviceBatch:
         return H, E, n, m, steps_h, coeffs
 
     @classmethod
-    def _from_rollout(cls, obs, act, rew, done, terminated, steps_h, coeffs, dims, T, reuse):
+    def _from_rollout(cls, obs, act, rew, done, terminated, steps_h, coeffs, dims, T, reuse, carry=None):
         H, E, n, m = dims
         dev = obs.device
         K, st = _lib.calls(), _lib.stream_ptr()
@@ -696,7 +713,16 @@ class DeviceBatch:
             hs.copy_(torch.from_numpy(steps_h))
             steps_d = slot("ro_steps", E, torch.int64)
             steps_d.copy_(hs, non_blocking=True)
-        K.mjrl_rollout_segments(done, terminated, steps_d, H, E, T, env_row, off, term, counts, seg, st)
+        t0 = env_path = None
+        if carry is None:
+            K.mjrl_rollout_segments(done, terminated, steps_d, H, E, T, env_row, off, term, counts, seg, st)
+        else:
+            # the same three launches; carry.episode_steps is read and rewritten in place
+            # (one slot for both tables: the host work here delays the pack's launch)
+            tabs = slot("ro_carry", T + E + 1, torch.int64, out)
+            t0, env_path = tabs[:T], tabs[T:]
+            K.mjrl_rollout_segments_carry(done, terminated, steps_d, H, E, T, carry.episode_steps, env_row, off, term,
+                                          t0, env_path, carry.episode_steps, counts, seg, st)
         # the one readback: (P, T) and the head of the path table, as many entries as
         # twice the most paths a call has had (at least two per env)
         cap = min(T, max(_STAGING.rollout_paths, 2 * E + 64))
@@ -729,10 +755,16 @@ class DeviceBatch:
         if coeffs is not None and T > 0:
             # LinearBaseline.predict on the packed rows (as from_paths' device predict)
             c = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64)).to(dev)
-            fn = K.mjrl_linear_baseline_f32 if o.dtype == torch.float32 else K.mjrl_linear_baseline
-            fn(o, T, n, off, P, c, base, st)
+            if t0 is None:
+                fn = K.mjrl_linear_baseline_f32 if o.dtype == torch.float32 else K.mjrl_linear_baseline
+                fn(o, T, n, off, P, c, base, st)
+            else:
+                fn = K.mjrl_linear_baseline_f32_t0 if o.dtype == torch.float32 else K.mjrl_linear_baseline_t0
+                fn(o, T, n, off, t0, P, c, base, st)
         b = cls(o, a, r, base, off, term, obs_range=orange)
         b.lengths = lengths
+        if t0 is not None:
+            b.path_t0, b.env_path = t0[:P], env_path
         return b
 
     def obs_lo(self, paths=None, reuse=True):
@@ -1084,6 +1116,18 @@ class UpdateEngine:
         fn(batch.rewards, base, batch.path_off, batch.terminated, batch.P, float(gamma),
            float(gae_lambda) if use_gae else 0.0, int(use_gae), w["ret"], w["adv64"], w["path_ret"], st)
         return w["ret"][:batch.T], w["adv64"][:batch.T]
+
+    @_on_device
+    def seed_returns(self, batch, gamma, stream=None):
+        """Rewrites the returns of the batch's unterminated paths in ws['ret'] (left by
+        returns_advantages / update) as discount_sum(rewards, gamma, terminal = the
+        path's last baseline prediction), bit for bit (mjrl_returns_seeded): the fit
+        targets of open fragments continue past the cut as GAE's b1[-1] = b[-1]
+        does.  Terminated paths keep their returns."""
+        st = stream if stream is not None else _lib.stream_ptr()
+        self.K.mjrl_returns_seeded(batch.rewards, self._baseline_of(batch), batch.path_off, batch.terminated, batch.P,
+                                   float(gamma), self.ws["ret"], st)
+        return self.ws["ret"][:batch.T]
 
     @staticmethod
     def _baseline_of(batch):
@@ -1554,7 +1598,9 @@ class UpdateEngine:
         baseline._coeffs; with return_errors, returns (error_before, error_after)
         computed from device residuals as the reference does.  obs_lo: the low
         halves of f32-staged observations (DeviceBatch.obs_lo): the features are
-        then formed from hi + lo, the sampler's f64 values to 2^-48."""
+        then formed from hi + lo, the sampler's f64 values to 2^-48.  A batch with
+        path_t0 (from_rollout(carry=)) is fitted with each path's time origin
+        (mjrl_linear_baseline_gram_t0 / _residual_t0)."""
         K = self.K
         st = _lib.stream_ptr()
         n, T, P = int(batch.obs.shape[1]), batch.T, batch.P
@@ -1578,16 +1624,23 @@ class UpdateEngine:
                         (False, True, True): ("_f32x2", True), (True, False, False): ("", False),
                         (True, True, False): ("_f32", True), (True, True, True): ("_f32", True)}[
             (bool(quadratic), f32, has_lo)]
+        t0 = getattr(batch, "path_t0", None)
+        if t0 is not None:
+            if quadratic or pair:
+                raise ValueError("fit_%s_baseline: the batch has a time origin per path (from_rollout(carry=)); "
+                                 "only the LinearBaseline fit on its own rows takes one" % kind)
+            suffix += "_t0"
         gram_fn = getattr(K, "mjrl_%s_baseline_gram%s" % (kind, suffix))
         res_fn = getattr(K, "mjrl_%s_baseline_residual%s" % (kind, suffix))
         obs_args = (batch.obs, obs_lo if has_lo else None) if pair else (batch.obs,)
-        gram_fn(*obs_args, y, T, n, batch.path_off, P, scratch, gram, st)
+        off_args = (batch.path_off,) if t0 is None else (batch.path_off, t0)
+        gram_fn(*obs_args, y, T, n, *off_args, P, scratch, gram, st)
         self.comm.allreduce_sum(gram)
 
         def sse(coeffs):
             r = torch.empty(max(T, 1), **f64)
             c = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64)).to(self.device)
-            res_fn(*obs_args, y, T, n, batch.path_off, P, c, scratch, r, st)
+            res_fn(*obs_args, y, T, n, *off_args, P, c, scratch, r, st)
             out = torch.zeros(8, **f64)
             part = torch.empty(4 * 256, **f64)
             K.mjrl_moments(r, T, None, part, out, st)

@@ -23,9 +23,23 @@ def _scatter(paths, key, values):
         i += H
 
 
-def compute_returns(paths, gamma):
+def compute_returns(paths, gamma, bootstrap=False):
+    """bootstrap: the returns of a path that is not terminated continue past its cut
+    with its last baseline prediction, discount_sum(rewards, gamma, terminal =
+    path["baseline"][-1]) (GAE's b1[-1] = b[-1] convention, process_samples.py:24-27;
+    the reference's discount_sum has the terminal argument and never passes it);
+    a terminated path's terminal stays 0.  Needs path["baseline"]."""
     lengths = [len(p["rewards"]) for p in paths]
-    ret, _ = device_returns_advantages(_cat(paths, "rewards"), None, lengths, [False] * len(paths), gamma, None)
+    rew = _cat(paths, "rewards")
+    if bootstrap:
+        # the seed enters as discount_sum's first step does: x[-1] + gamma * terminal
+        rew = rew.copy()
+        end = np.cumsum(lengths)
+        for p, e, L in zip(paths, end, lengths):
+            terminal = 0.0 if p.get("terminated", False) else (float(p["baseline"][-1]) if L else 0.0)
+            if L and terminal != 0.0:
+                rew[e - 1] = rew[e - 1] + gamma * terminal
+    ret, _ = device_returns_advantages(rew, None, lengths, [False] * len(paths), gamma, None)
     _scatter(paths, "returns", ret)
 
 

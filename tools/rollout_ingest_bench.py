@@ -2,7 +2,7 @@
 the Humanoid shape: E = 1000 environments x H = 1000 steps (1M rows, n = 376,
 m = 17, float32), every environment done every 250 - 1000 steps.
 
-    python tools/rollout_ingest_bench.py [--envs 1000] [--steps 1000] [--n 376] [--m 17] [--alternations 5]
+    python tools/rollout_ingest_bench.py [--envs 1000] [--steps 1000] [--n 376] [--m 17] [--alternations 5] [--carry]
 
 One process times three things: from_rollout on the step-major device tensors,
 from_paths (float32 staging, reused buffers) on the equivalent host paths
@@ -12,7 +12,13 @@ warm-up round whose times are dropped, then `--alternations` rounds.  A call is
 timed on the host clock from its start to a device synchronise after it.  Prints
 the medians and ranges as one JSON line, with the pack's share of its floor
 (bytes read plus bytes written over 8 TB/s) and the ratio to from_paths; exits 1
-unless the median of from_rollout is below the minimum of from_paths.  Needs a GPU."""
+unless the median of from_rollout is below the minimum of from_paths.  --carry: every
+round also times from_rollout with a RolloutCarry (the episodes of the call before
+continued; the carry advances from round to round), mjrl_rollout_segments_carry alone
+and mjrl_returns_seeded alone on the rollout's paths (one open fragment per env), in
+the same alternation, and reports whether the carried route's median lies inside the
+plain route's own range; the round then ends with an untimed from_paths and kernel
+pair, so that both timed from_rollout calls follow the same work.  Needs a GPU."""
 import argparse
 import ctypes as C
 import json
@@ -39,6 +45,7 @@ def main():
     ap.add_argument("--n", type=int, default=376)
     ap.add_argument("--m", type=int, default=17)
     ap.add_argument("--alternations", type=int, default=5)
+    ap.add_argument("--carry", action="store_true", help="also time the carried route and the seeded returns")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -77,6 +84,11 @@ def main():
     def stage():
         return DeviceBatch.from_paths(paths, dev, obs_dtype=np.float32, reuse=True)
 
+    carry = RI.RolloutCarry(E, dev) if args.carry else None
+
+    def roll_carry():
+        return DeviceBatch.from_rollout(obs, act, rew, d_done, reuse=True, carry=carry)
+
     # the kernels alone, on buffers of their own
     K, st = _lib.calls(), _lib.stream_ptr()
     i64 = dict(dtype=torch.int64, device=dev)
@@ -100,7 +112,28 @@ def main():
         torch.cuda.synchronize()
         return ev[0].elapsed_time(ev[1]) / 1e3, ev[1].elapsed_time(ev[2]) / 1e3
 
+    if args.carry:
+        t0, env_path = torch.zeros(T, **i64), torch.zeros(E + 1, **i64)
+        steps_k = torch.zeros(E, **i64)
+        base = torch.randn(T, generator=g, device=dev, dtype=torch.float64)
+        rew64, ret = rew.double().t().contiguous().view(-1), torch.empty(T, dtype=torch.float64, device=dev)
+
+    def carry_kernels():
+        """after kernels(): off / term hold the rollout's path table"""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        K.mjrl_rollout_segments_carry(d_done, None, None, H, E, T, steps_k, env_row, off, term, t0, env_path, steps_k,
+                                      counts, seg, st)
+        ev[1].record()
+        ev[2].record()
+        K.mjrl_returns_seeded(rew64, base, off, term, P, 0.995, ret, st)
+        ev[3].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / 1e3, ev[2].elapsed_time(ev[3]) / 1e3
+
     times = dict(from_rollout=[], from_paths=[], segments=[], pack=[])
+    if args.carry:
+        times.update(from_rollout_carry=[], segments_carry=[], returns_seeded=[])
     for it in range(args.alternations + 1):   # round 0 warms up
         tr, b = sync_time(roll)
         assert (b.T, b.P) == (T, P)
@@ -110,6 +143,18 @@ def main():
         if it:
             for k, v in (("from_rollout", tr), ("from_paths", tp), ("segments", ts), ("pack", tk)):
                 times[k].append(v)
+        if args.carry:
+            tc, b = sync_time(roll_carry)
+            assert (b.T, b.P) == (T, P) and b.path_t0 is not None
+            tsc, trs = carry_kernels()
+            # the next round's plain call then follows what the carried one followed (50 ms
+            # of host staging, then the two kernels): a from_rollout that followed another
+            # one closely instead measured 0.10-0.12 ms faster, whichever route it took
+            stage()
+            kernels()
+            if it:
+                for k, v in (("from_rollout_carry", tc), ("segments_carry", tsc), ("returns_seeded", trs)):
+                    times[k].append(v)
     pack_bytes = T * (2 * 4 * (n + m) + 4 + 8)   # rows read and written, f32 reward in, f64 out
     floor = pack_bytes / HBM_BYTES_PER_S
     res = {k: summary(v) for k, v in times.items()}
@@ -119,6 +164,10 @@ def main():
                statistics.median(times["from_rollout"]))
     ok = statistics.median(times["from_rollout"]) < min(times["from_paths"])
     res["from_rollout_median_below_from_paths_min"] = ok
+    if args.carry:
+        med = statistics.median(times["from_rollout_carry"])
+        res["carry_median_inside_plain_range"] = min(times["from_rollout"]) <= med <= max(times["from_rollout"])
+        res["open_paths"] = int((term[:P] == 0).sum())
     print(json.dumps(res))
     return 0 if ok else 1
 
