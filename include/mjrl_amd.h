@@ -534,6 +534,35 @@ int mjrl_policy_mean_slots(const mjrl_shape* s, const double* obs64, const int32
                            const float* packed_theta, const float* in_shift, const float* in_scale,
                            const float* out_shift, const float* out_scale, float* mean, void* stream);
 
+/* ---- the device actor: policy actions for device rollouts ----
+ * policy.get_action (mjrl/policies/gaussian_mlp.py:91-98, gaussian_linear.py) for the
+ * E environments of a batched GPU simulator, noise included, in one launch:
+ *   mean[e] = mjrl_policy_mean's function of obs[e] (f32 [E][n], or f64 rounded to f32
+ *             on load with (float)x when obs_f64 = 1), the three layers as exact-f32
+ *             MFMA products over tiles of 16 rows (sums in another order than
+ *             mjrl_policy_mean's: equal up to f32 rounding, not bitwise);
+ *   eps[e][j] = the standard normal of (seed, step, env0 + e, j): Philox4x32-10 with
+ *             counter (step lo, step hi, (env0 + e) lo, j >> 2) and key (seed lo, seed
+ *             hi); the four words give columns 4b .. 4b + 3 by two Box-Muller pairs,
+ *             u1 = ((x >> 8) + 1) 2^-24, u2 = (x' >> 8) 2^-24, r = sqrt(-2 log u1),
+ *             th = f32(2 pi) u2, (r cos th, r sin th), all f32
+ *             (samplers/device_actor.py: noise_reference restates it in NumPy);
+ *   act[e][j] = mean + sigma[j] * eps as two separately rounded f32 operations
+ *             (sigma = float32(exp(log_std)), formed by the caller); sigma null: the
+ *             mean (get_action's `evaluation` entry).
+ * act [E][m] and obs_copy [E][n] (a verbatim copy of obs, or null) are in the
+ * observations' dtype (f64: (double) of the f32 value); mean and eps f32 [E][m] or
+ * null.  A row's outputs depend on its own observation and on (seed, step, env0 + e)
+ * only, so sub-batches and split rollouts reproduce the full call bit for bit.  Only
+ * rows < E are written.  All pointers are device pointers; stream-ordered, no
+ * allocation, no synchronisation.  MJRL_EINVAL before any launch for a null s,
+ * packed_theta, or (E > 0) obs / act, E < 0, step < 0, obs_f64 not 0 or 1, or one of
+ * a shift / scale pair null; E == 0 is MJRL_OK without a launch. */
+int mjrl_policy_act(const mjrl_shape* s, const void* obs, int32_t obs_f64, int64_t E, const float* packed_theta,
+                    const float* in_shift, const float* in_scale, const float* out_shift, const float* out_scale,
+                    const float* sigma, uint64_t seed, int64_t step, int64_t env0, void* act, float* mean,
+                    float* eps, void* obs_copy, void* stream);
+
 /* ---- MLPBaseline value features formed while sampling (streamed staging) ----
  * The first n columns of mjrl/baselines/mlp_baseline.py:37-56's features,
  * float32(clip(x, -10, 10) / 10) of the sampler's f64 observation x (no f32 image of

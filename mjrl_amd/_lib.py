@@ -157,6 +157,7 @@ SIGNATURES = {
     "mjrl_trpo_trial": [SP, P, P, F32, P, P, P, P, F64, F64, I32, I32, P, P, P],
     "mjrl_policy_mean": [SP, P, I64, P, P, P, P, P, P, P],
     "mjrl_policy_mean_slots": [SP, P, P, I64, I64, P, P, P, P, P, P, P],
+    "mjrl_policy_act": [SP, P, I32, I64, P, P, P, P, P, P, C.c_uint64, I64, I64, P, P, P, P, P],
     "mjrl_value_features_slots": [P, P, P, I64, I64, I32, I64, P, P],
     "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
     "mjrl_value_features_finish_runs": [P, P, I64, I32, I64, I64, I64, P, P, P],

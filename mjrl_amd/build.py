@@ -21,7 +21,7 @@ FLAGS = [
     "-ffp-contract=off",          # keep the reference's multiply-then-add order
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
 ]
-SOURCES = ["batch.hip", "policy.hip", "cg.hip", "baseline.hip", "rollout.hip", "ingest.hip", "value_fit.hip",
+SOURCES = ["batch.hip", "policy.hip", "cg.hip", "baseline.hip", "rollout.hip", "act.hip", "ingest.hip", "value_fit.hip",
            "policy_fit.hip", "policy_fit_wide.hip"]
 # host-only C++ (the staging conversion of csrc/stage.cpp), built with g++
 HOST_SOURCES = ["stage.cpp"]

@@ -1,0 +1,1 @@
+from .device_actor import DeviceActor, DeviceRollout  # noqa: F401
