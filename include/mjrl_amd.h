@@ -808,6 +808,31 @@ int mjrl_policy_mse_wide_epoch(const mjrl_policy_fit_data* data, const int64_t* 
                                const mjrl_mean_net* net, const mjrl_adam* hp, float* scratch, float* grad_out,
                                float* loss_out, void* stream);
 
+/* ---- the same steps for minibatches of up to 16384 rows (csrc/policy_fit_rows.hip) ----
+ * mjrl_policy_fit_epoch with 1 <= bs <= MJRL_POLICY_FIT_ROWS_MAX_BS (1 <= m, h0, h1 <= 64 as
+ * there; the BC and PPO heads, the latter with ll_old or old_log_std; there is no MSE form): the
+ * same structures, the same step, the same meaning of idx [nmb][bs] (entries may repeat), net,
+ * hp, grad_out [nmb][d] and loss_out [nmb].  A step is sliced over row tiles and is two launches
+ * of its own, so there is no steps_per_launch: one workgroup per 64 rows runs the forward chain,
+ * the loss head (the mean divides by the whole bs) and the backward chain of its rows and stores
+ * its part of the gradient [d] and of the loss; behind the kernel boundary, element by element,
+ * the parts are summed in fp64 in ascending tile order and rounded once to f32, then Adam steps
+ * as above.  Every dependency between workgroups is a kernel boundary; no launch waits on another
+ * workgroup.  The parts live in the scratch: mjrl_policy_fit_rows_scratch floats (at least
+ * ceil(bs / 64) d, never less for a larger bs; MJRL_EINVAL for n <= 0, m / h0 / h1 outside 1..64,
+ * bs outside 1..16384 or a null result), 16-byte aligned, of which nothing but float [0], the
+ * last step's loss, means anything after a call.  Exact-f32 MFMA, every sum in one fixed order, no
+ * atomics: the same state and arguments give the same bits, however nmb steps are split over
+ * calls (step0 advanced).  With bs <= 64 there is one tile, and the parameters, the moments,
+ * grad_out and loss_out carry mjrl_policy_fit_epoch's bits.  Never allocates, never
+ * synchronises.  MJRL_EINVAL before any launch for what mjrl_policy_fit_epoch refuses, with bs
+ * outside 1..16384; nmb == 0 is MJRL_OK without a launch. */
+#define MJRL_POLICY_FIT_ROWS_MAX_BS 16384
+int mjrl_policy_fit_rows_scratch(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int64_t* floats);
+int mjrl_policy_fit_rows_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,
+                               const mjrl_policy_net* net, const mjrl_adam* hp, float* scratch, float* grad_out,
+                               float* loss_out, void* stream);
+
 /* ---- host staging of sampler paths (base_sampler.py:76-83,
  * npg_cg.py:87-89 concatenate) — HOST memory, runs on the calling CPU thread ----
  * dst[rows][n] = float(src) (round to nearest, as torch .float()), and when cmin /

@@ -70,6 +70,7 @@ class PolicyFitData(C.Structure):
 
 
 POLICY_FIT_BC, POLICY_FIT_PPO = 0, 1   # MJRL_POLICY_FIT_BC / _PPO
+POLICY_FIT_ROWS_MAX_BS = 16384         # MJRL_POLICY_FIT_ROWS_MAX_BS
 
 
 class Adam(C.Structure):
@@ -177,6 +178,9 @@ SIGNATURES = {
     "mjrl_policy_fit_wide_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(PolicyNet), C.POINTER(Adam), P,
                                    P, P, P],
     "mjrl_policy_mse_wide_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(MeanNet), C.POINTER(Adam), P,
+                                   P, P, P],
+    "mjrl_policy_fit_rows_scratch": [I32, I32, I32, I32, I32, C.POINTER(I64)],
+    "mjrl_policy_fit_rows_epoch": [C.POINTER(PolicyFitData), P, I64, I32, C.POINTER(PolicyNet), C.POINTER(Adam), P,
                                    P, P, P],
     "mjrl_build_flags": [],
     "mjrl_host_stage_f64": [P, I64, I32, P, P, P],

@@ -22,11 +22,16 @@ parameters and the device optimizer's moments: DeviceTrainer.fused_epoch, limits
 in check_fit_backend.  fit_backend = "hip_wide" (opt-in too) is the
 same step sliced over workgroups for hidden layers up to 256 units wide
 (csrc/policy_fit_wide.hip, mjrl_policy_fit_wide_epoch): fused_epoch(..., wide=True).
+fit_backend = "hip_rows" (opt-in too) is the same step sliced over row tiles, one workgroup
+per 64 rows, for minibatches of up to 16384 rows at the narrow backend's widths
+(csrc/policy_fit_rows.hip, mjrl_policy_fit_rows_epoch): fused_epoch(..., rows=True).
 
 MSE behaviour cloning (behavior_cloning_2.py) trains policy.model.parameters()
 alone: DeviceTrainer(..., params=...) mirrors that list instead of
 policy.trainable_params, and fused_epoch("mse", ...) is mjrl_policy_mse_epoch.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -36,6 +41,9 @@ from .._device_fit import HIP_MAX_BATCH
 
 # PPO's, BC's and behavior_cloning_2.BC's fit_backend (MLPBaseline keeps _device_fit.FIT_BACKENDS)
 POLICY_FIT_BACKENDS = ("torch", "hip", "hip_wide")
+# PPO's and BC's fourth: the row-tiled kernels of csrc/policy_fit_rows.hip (the MSE head has none)
+ROWS_BACKEND = "hip_rows"
+HIP_ROWS_MAX_BATCH = 16384   # rows of a minibatch they take (MJRL_POLICY_FIT_ROWS_MAX_BS)
 
 LOG_2PI = float(np.log(2 * np.pi))
 
@@ -165,7 +173,7 @@ class DeviceTrainer:
 
     # ---- the fused route (fit_backend = "hip") -------------------------------------------
     def fused_epoch(self, kind, obs, act, idx_batches, adv=None, ll_old=None, old_log_std=None, clip=0.0,
-                    wide=False):
+                    wide=False, rows=False):
         """epoch()'s steps as one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on
         the current stream: self.params and the device optimizer's exp_avg /
         exp_avg_sq are updated in place, then every step counter advances by nmb.
@@ -175,25 +183,39 @@ class DeviceTrainer:
         policy.model.parameters() (behavior_cloning_2.py), obs / act alone.
         wide: the sliced kernels of csrc/policy_fit_wide.hip (hidden layers up to 256
         units; mjrl_policy_fit_wide_epoch / mjrl_policy_mse_wide_epoch) on the same
-        parameters and moments, with a scratch of their own."""
+        parameters and moments, with a scratch of their own.
+        rows: the row-tiled kernels of csrc/policy_fit_rows.hip (minibatches of up to 16384
+        rows, "bc" and "ppo"; mjrl_policy_fit_rows_epoch), with a scratch of their own that
+        grows with the minibatch."""
         from .. import _lib
         nmb, bs = int(idx_batches.shape[0]), int(idx_batches.shape[1])
         if nmb == 0:
             return
         dev = self.device
         _fit.ensure_adam_state(self.opt, self.params, dev)   # a fresh optimizer has no state yet
-        rows = [t for t in (obs, act, adv, ll_old, old_log_std) if t is not None]
-        if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev for t in rows) \
+        given = [t for t in (obs, act, adv, ll_old, old_log_std) if t is not None]
+        if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev for t in given) \
                 or obs.shape[1] != self.policy.n or act.shape[1] != self.policy.m:
             raise ValueError("the fused policy fit takes contiguous f32 rows obs [T][n], act [T][m] on the trainer's device")
         idx_batches = idx_batches.contiguous()
-        K = _lib.calls()
-        skey = "_hip_wide_scratch" if wide else "_hip_scratch"
-        scratch = _fit.scratch(getattr(self, skey, None),
-                               K.mjrl_policy_fit_wide_scratch if wide else K.mjrl_policy_fit_scratch,
-                               (self.policy.n, self.policy.m, *self.policy.hidden, bs), dev)
-        setattr(self, skey, scratch)
         mse = kind == "mse"
+        if rows and (wide or mse):
+            raise ValueError("the row-tiled policy fit has neither a wide nor an MSE form")
+        K = _lib.calls()
+        dims = (self.policy.n, self.policy.m, *self.policy.hidden, bs)
+        if rows:
+            # the slab of the tiles' gradients grows with bs: a later call may need a larger one
+            skey, scratch = "_hip_rows_scratch", getattr(self, "_hip_rows_scratch", None)
+            need = C.c_int64()
+            K.mjrl_policy_fit_rows_scratch(*dims, need)
+            if scratch is not None and scratch.numel() < need.value:
+                scratch = None
+            scratch = _fit.scratch(scratch, K.mjrl_policy_fit_rows_scratch, dims, dev)
+        else:
+            skey = "_hip_wide_scratch" if wide else "_hip_scratch"
+            scratch = _fit.scratch(getattr(self, skey, None),
+                                   K.mjrl_policy_fit_wide_scratch if wide else K.mjrl_policy_fit_scratch, dims, dev)
+        setattr(self, skey, scratch)
         if len(self.params) != (6 if mse else 7):
             raise ValueError("the fused %s fit trains %s" % (kind, "policy.model.parameters()" if mse
                                                              else "policy.trainable_params"))
@@ -206,7 +228,9 @@ class DeviceTrainer:
         hp = _fit.adam_hp(self.opt, self.params)
         with torch.cuda.device(dev):
             stream = _lib.stream_ptr(torch.cuda.current_stream(dev))
-            if wide:
+            if rows:
+                K.mjrl_policy_fit_rows_epoch(data, idx_batches, nmb, bs, net, hp, scratch, None, None, stream)
+            elif wide:
                 (K.mjrl_policy_mse_wide_epoch if mse else K.mjrl_policy_fit_wide_epoch)(
                     data, idx_batches, nmb, bs, net, hp, scratch, None, None, stream)
             else:
@@ -221,17 +245,24 @@ HIP_WIDE_MAX_WIDTH = 256   # the sliced kernels' largest hidden width (csrc/poli
 
 def check_fit_backend(who, backend, policy, optimizer, mb_size, device, mean_only=False):
     """The fused route's limits, each a ValueError naming it, before anything
-    touches the GPU library.  Returns True when the backend is "hip" or "hip_wide"
-    (the same checks, hidden widths 1..256).
+    touches the GPU library.  Returns True when the backend is "hip", "hip_wide"
+    (the same checks, hidden widths 1..256) or "hip_rows" (the same checks, minibatches of
+    1..16384 rows; not with mean_only).
     mean_only: the MSE fit's net, the optimizer over policy.model.parameters() alone."""
-    if backend not in POLICY_FIT_BACKENDS:
-        raise ValueError("%s.fit_backend must be one of %s, not %r" % (who, POLICY_FIT_BACKENDS, backend))
+    if backend not in POLICY_FIT_BACKENDS and backend != ROWS_BACKEND:
+        raise ValueError("%s.fit_backend must be one of %s, not %r" % (who, POLICY_FIT_BACKENDS, backend)
+                         + ("" if mean_only else ' (or "%s" for minibatches above %d rows)'
+                            % (ROWS_BACKEND, HIP_MAX_BATCH)))
     if backend == "torch":
         return False
     pre = '%s.fit_backend = "%s"' % (who, backend)
+    if backend == ROWS_BACKEND and mean_only:
+        raise ValueError("%s: the MSE head has no row-tiled kernel (csrc/policy_fit_rows.hip builds the BC and "
+                         "PPO heads); take \"hip\" or \"hip_wide\"" % pre)
     max_h = HIP_WIDE_MAX_WIDTH if backend == "hip_wide" else HIP_MAX_WIDTH
-    if not 1 <= int(mb_size) <= HIP_MAX_BATCH:
-        raise ValueError("%s takes minibatches of 1..%d rows, not %d" % (pre, HIP_MAX_BATCH, mb_size))
+    max_b = HIP_ROWS_MAX_BATCH if backend == ROWS_BACKEND else HIP_MAX_BATCH
+    if not 1 <= int(mb_size) <= max_b:
+        raise ValueError("%s takes minibatches of 1..%d rows, not %d" % (pre, max_b, mb_size))
     hidden = policy.hidden
     if hidden is None:
         raise ValueError("%s trains the Gaussian MLP policy (two hidden layers), not a LinearPolicy" % pre)

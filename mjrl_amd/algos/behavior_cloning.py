@@ -14,7 +14,9 @@ The expert rows are staged to the device once per train() call.
 fit_backend = "hip" (opt-in, per instance or on the class) runs the minibatch
 steps as the fused kernel of csrc/policy_fit.hip instead (batch_size <= 64, MLP
 policies up to 64 units wide); fit_backend = "hip_wide" as the sliced
-kernels of csrc/policy_fit_wide.hip (hidden layers up to 256 units).
+kernels of csrc/policy_fit_wide.hip (hidden layers up to 256 units); fit_backend =
+"hip_rows" as the row-tiled kernels of csrc/policy_fit_rows.hip (batch_size <= 16384,
+widths up to 64).
 """
 import logging
 import time as timer
@@ -23,7 +25,7 @@ import numpy as np
 import torch
 
 from ..utils.logger import DataLog
-from ._device_sgd import DeviceTrainer, check_fit_backend, choice_batches, default_device
+from ._device_sgd import ROWS_BACKEND, DeviceTrainer, check_fit_backend, choice_batches, default_device
 
 logging.disable(logging.CRITICAL)
 
@@ -31,7 +33,8 @@ logging.disable(logging.CRITICAL)
 class BC:
     # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
     # csrc/policy_fit.hip (opt-in, per instance or on the class); "hip_wide": the sliced
-    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too)
+    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too); "hip_rows": the
+    # row-tiled kernels of csrc/policy_fit_rows.hip for minibatches of up to 16384 rows (opt-in too)
     fit_backend = "torch"
 
     def __init__(self, expert_paths, policy, epochs=5, batch_size=64, lr=1e-3, optimizer=None, device=None):
@@ -100,7 +103,8 @@ class BC:
             self.logger.log_kv("time", timer.time() - ts)
             batches = choice_batches(num_samples, self.mb_size, tr.device)
             if hip:
-                tr.fused_epoch("bc", O, A, batches, wide=self.fit_backend == "hip_wide")
+                tr.fused_epoch("bc", O, A, batches, wide=self.fit_backend == "hip_wide",
+                               rows=self.fit_backend == ROWS_BACKEND)
             else:
                 tr.epoch(("bc", self._ncall), mb_loss, batches)
         tr.push()

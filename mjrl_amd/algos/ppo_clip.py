@@ -18,7 +18,8 @@ advantages to train_from_paths.  fit_backend = "hip" (opt-in, per instance or on
 the class) runs the minibatch steps as the fused kernel of csrc/policy_fit.hip
 instead (mb_size <= 64, MLP policies up to 64 units wide), fit_backend =
 "hip_wide" as the sliced kernels of csrc/policy_fit_wide.hip (hidden layers up to 256
-units).  Single process: the minibatch order is global,
+units), fit_backend = "hip_rows" as the row-tiled kernels of csrc/policy_fit_rows.hip
+(mb_size <= 16384, widths up to 64).  Single process: the minibatch order is global,
 so a sharded PPO is not offered (comm must be local).
 """
 import time as timer
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 
 from .batch_reinforce import BatchREINFORCE
-from ._device_sgd import DeviceTrainer, check_fit_backend, choice_batches
+from ._device_sgd import ROWS_BACKEND, DeviceTrainer, check_fit_backend, choice_batches
 from ..utils.logger import DataLog
 
 
@@ -35,7 +36,8 @@ class PPO(BatchREINFORCE):
     _poolable = False   # the minibatch order is global: one process, even with MJRL_AMD_DEVICES set
     # "torch": a captured graph of torch ops per minibatch step; "hip": the fused kernel of
     # csrc/policy_fit.hip (opt-in, per instance or on the class); "hip_wide": the sliced
-    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too)
+    # kernels of csrc/policy_fit_wide.hip for hidden layers up to 256 units (opt-in too); "hip_rows": the
+    # row-tiled kernels of csrc/policy_fit_rows.hip for minibatches of up to 16384 rows (opt-in too)
     fit_backend = "torch"
 
     def __init__(self, env, policy, baseline, clip_coef=0.2, epochs=10, mb_size=64, learn_rate=3e-4, seed=0,
@@ -152,7 +154,7 @@ class PPO(BatchREINFORCE):
             if hip:
                 tr.fused_epoch("ppo", O, A, batches, adv=ADV, ll_old=None if aliased else LL_old,
                                old_log_std=old_dev[-1].contiguous() if aliased else None, clip=c,
-                               wide=self.fit_backend == "hip_wide")
+                               wide=self.fit_backend == "hip_wide", rows=self.fit_backend == ROWS_BACKEND)
             else:
                 tr.epoch(("ppo", self._ncall), mb_loss, batches)
         tr.push()

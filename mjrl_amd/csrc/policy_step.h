@@ -1,10 +1,12 @@
-// policy_step.h — what the two fused minibatch Adam fits of the Gaussian MLP policy share
+// policy_step.h — what the fused minibatch Adam fits of the Gaussian MLP policy share
 // (policy_fit.hip: one workgroup, widths up to 64; policy_fit_wide.hip: three kernels a step,
-// widths up to 256): the argument block, the gathered X tile, the weight-gradient job, the loss
+// widths up to 256; policy_fit_rows.hip: one workgroup per 64 rows of a minibatch of up to 16384,
+// two kernels a step): the argument block, the gathered X tile, the weight-gradient job, the loss
 // heads with log_std's part of the step, and the host's checks and argument filling.
 //
 // The policy is Linear(n, h0) - tanh - Linear(h0, h1) - tanh - Linear(h1, m) plus log_std[m] in
-// torch's layouts and order.  A step trains on bs <= 64 rows named by a device index buffer; rows
+// torch's layouts and order.  A step trains on bs <= 64 rows named by a device index buffer
+// (policy_fit_rows.hip: a row tile holds 64 of a step's bs rows); rows
 // bs .. 63 and a row whose index is outside [0, T) are masked: nothing of obs / act / adv / ll_old
 // is read for them, their dL/dLL is 0, the mean still divides by bs.  template <bool MSE>: false,
 // BC's -mean LL or PPO's clipped surrogate on the seven tensors; true, the MSE head of
@@ -131,6 +133,33 @@ __device__ __forceinline__ void wgrad_job(const StepArgs& a, const AdamK& hp, fl
             const int unit = 16 * ublk + 4 * q + i;
             if (unit >= U) continue;
             wgrad_tail(pm[i], acc[i], unit, K, col, hp, pw, mw, vw, pb, mb, vb, grad, gw, gb);
+        }
+    }
+}
+
+// wgrad_job's product without the step (policy_fit_rows.hip: Adam follows a kernel boundary, on
+// the gradients of all row tiles folded): the job's accumulator, formed exactly as there, goes to
+// its flat place gw / gb of one row tile's [d] slice of the scratch, which starts at float off.
+__device__ __forceinline__ void wgrad_store_job(const StepArgs& a, int64_t off, int U, int K, int ublk, int col0,
+                                                const float* gl, int gld, int goff, const float* bl, int bld,
+                                                int boff, int64_t gw, int64_t gb, int r, int q) {
+    const int col = col0 + r;
+    const int lc = col < K ? col - boff : 0;   // a tile column that exists (col >= K: not used)
+    floatx4 acc = zero4();
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int row = 4 * s + q;
+        const float b = bl[row * bld + lc];
+        acc = mfma4(gl[row * gld + goff + r], col < K ? b : (col == K ? 1.f : 0.f), acc);
+    }
+    if (col <= K) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int unit = 16 * ublk + 4 * q + i;
+            if (unit >= U) continue;
+            const int64_t e = off + (col < K ? gw + (int64_t)unit * K + col : gb + unit);
+            MJRL_SLAB_CHECK(e, a.scap);
+            a.scratch[e] = acc[i];
         }
     }
 }
@@ -291,25 +320,28 @@ __device__ __forceinline__ void log_std_adam(const StepArgs& a, const AdamK& hp,
     a.v[6][lane] = v1;
 }
 
-// ---- host: the sizes a file's entry points take (hidden widths up to max_hidden) ----------------
-inline bool widths_ok(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int max_hidden) {
+// ---- host: the sizes a file's entry points take (hidden widths up to max_hidden, minibatches
+// of up to max_rows rows: PS_ROWS but for the row-tiled policy_fit_rows.hip) ----------------------
+inline bool widths_ok(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int max_hidden,
+                      int max_rows = PS_ROWS) {
     return n > 0 && m >= 1 && m <= PS_NA && h0 >= 1 && h0 <= max_hidden && h1 >= 1 && h1 <= max_hidden && bs >= 1 &&
-           bs <= PS_ROWS;
+           bs <= max_rows;
 }
 
 // the body of a scratch query
 inline int scratch_query(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int max_hidden, int64_t need,
-                         int64_t* floats) {
-    if (!widths_ok(n, m, h0, h1, bs, max_hidden) || !floats) return MJRL_EINVAL;
+                         int64_t* floats, int max_rows = PS_ROWS) {
+    if (!widths_ok(n, m, h0, h1, bs, max_hidden, max_rows) || !floats) return MJRL_EINVAL;
     *floats = need;
     return MJRL_OK;
 }
 
 // the checks the entry points make on what they all read; nmb > 0: the pointers too
-inline bool sizes_ok(const mjrl_policy_fit_data* data, int64_t nmb, int32_t bs, int max_hidden) {
+inline bool sizes_ok(const mjrl_policy_fit_data* data, int64_t nmb, int32_t bs, int max_hidden,
+                     int max_rows = PS_ROWS) {
     if (!data || nmb < 0 || data->T < 0) return false;
     // n <= 2^24: the kernels index a tensor's elements with 32 bits
-    return widths_ok(data->n, data->m, data->h0, data->h1, bs, max_hidden) && data->n <= (1 << 24);
+    return widths_ok(data->n, data->m, data->h0, data->h1, bs, max_hidden, max_rows) && data->n <= (1 << 24);
 }
 
 inline bool pointers_ok(const mjrl_policy_fit_data* data, const int64_t* idx, const void* net, const mjrl_adam* hp,
@@ -324,8 +356,9 @@ inline bool pointers_ok(const mjrl_policy_fit_data* data, const int64_t* idx, co
 // part.  MJRL_OK with nmb == 0: nothing was filled and nothing is to run.
 template <bool MSE, class Net>
 inline int step_args(StepArgs& a, const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb,
-                     int32_t bs, const Net* net, const mjrl_adam* hp, float* scratch, int64_t scap, int max_hidden) {
-    if (!sizes_ok(data, nmb, bs, max_hidden)) return MJRL_EINVAL;
+                     int32_t bs, const Net* net, const mjrl_adam* hp, float* scratch, int64_t scap, int max_hidden,
+                     int max_rows = PS_ROWS) {
+    if (!sizes_ok(data, nmb, bs, max_hidden, max_rows)) return MJRL_EINVAL;
     const bool ppo = !MSE && data->kind == MJRL_POLICY_FIT_PPO;
     if (!MSE && data->kind != MJRL_POLICY_FIT_BC && !ppo) return MJRL_EINVAL;
     if (ppo && (!data->ll_old == !data->old_log_std)) return MJRL_EINVAL;

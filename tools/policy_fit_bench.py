@@ -1,6 +1,6 @@
 """PPO.train_from_paths on synthetic paths with fit_backend "torch" (a captured graph
-of torch ops per minibatch step) against a fused backend ("hip", csrc/policy_fit.hip, or
-"hip_wide", csrc/policy_fit_wide.hip), at these shapes:
+of torch ops per minibatch step) against a fused backend ("hip", csrc/policy_fit.hip,
+"hip_wide", csrc/policy_fit_wide.hip, or "hip_rows", csrc/policy_fit_rows.hip), at these shapes:
 
     swimmer      n = 8, m = 2, hidden (64, 64), 25 paths of 500 rows, class defaults
                  (10 epochs of 195 minibatches of 64 rows: 1,950 Adam steps a call)
@@ -13,10 +13,12 @@ of torch ops per minibatch step) against a fused backend ("hip", csrc/policy_fit
 
     python tools/policy_fit_bench.py [--alternations 3] [--timeout 300] [--shapes swimmer,humanoid]
                                      [--algo ppo|bc_mse] [--backends torch,hip] [--hidden H0,H1]
+                                     [--mb-size ROWS]
 
 --backends names the two backends that alternate (default torch,hip; torch,hip_wide for the wide
 shapes, hip,hip_wide to compare the two fused ones where both run); --hidden overrides the
-shapes' hidden sizes.
+shapes' hidden sizes; --mb-size the minibatch rows (the classes' default is 64; "hip_rows" takes
+up to 16384, the other fused backends 64; the steps a call runs shrink accordingly).
 
 --algo bc_mse times behavior_cloning_2.BC.train() (the MSE head, mjrl_policy_mse_epoch)
 instead, on synthetic expert paths of the same sizes: class defaults at swimmer (5
@@ -48,7 +50,7 @@ SHAPES = {   # n, m, paths, rows per path, PPO keyword arguments, hidden sizes
     "halfcheetah": (17, 6, 100, 1000, dict(epochs=2), (128, 128)),
     "door": (39, 28, 200, 200, dict(epochs=4), (256, 256)),
 }
-BACKENDS = ("torch", "hip", "hip_wide")
+BACKENDS = ("torch", "hip", "hip_wide", "hip_rows")
 
 
 def child(args):
@@ -63,6 +65,8 @@ def child(args):
         hidden = tuple(int(h) for h in args.hidden.split(","))
     policy = MLP(EnvSpec(n, m, H, 1), hidden_sizes=hidden, seed=1, init_log_std=-0.5)
     mse = args.algo == "bc_mse"
+    if args.mb_size:
+        kw = dict(kw, **{"batch_size" if mse else "mb_size": args.mb_size})
     if mse:
         from mjrl_amd.algos.behavior_cloning_2 import BC
         # the constructor reads its paths for the transformations; every timed call gets its own
@@ -105,7 +109,8 @@ def child(args):
     steps = agent.epochs * int(npaths * H / agent.mb_size)
     theta = policy.get_param_values()
     print(json.dumps(dict(backend=args.child, shape=args.shape, call_s=times[1], epochs_s=epochs_s[1],
-                          warmup_s=times[0], steps=steps, hidden=list(hidden), param_norm=float(np.linalg.norm(theta)),
+                          warmup_s=times[0], steps=steps, hidden=list(hidden), mb_size=agent.mb_size,
+                          param_norm=float(np.linalg.norm(theta)),
                           finite=bool(np.all(np.isfinite(theta))))))
 
 
@@ -118,6 +123,7 @@ def main():
     ap.add_argument("--shape", default="swimmer", help=argparse.SUPPRESS)
     ap.add_argument("--backends", default="torch,hip", help="the two backends that alternate")
     ap.add_argument("--hidden", default="", help="H0,H1 instead of the shapes' own hidden sizes")
+    ap.add_argument("--mb-size", type=int, default=0, help="minibatch rows instead of the classes' 64")
     ap.add_argument("--child", choices=BACKENDS, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
@@ -131,11 +137,11 @@ def main():
         res["algo"] = args.algo
     for shape in args.shapes.split(","):
         runs = {base: [], other: []}
-        steps, norm, hidden = 0, {}, None
+        steps, norm, hidden, mb = 0, {}, None, None
         for pair in range(args.alternations + 1):
             for backend in pair_of:
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", backend, "--shape", shape,
-                       "--algo", args.algo, "--hidden", args.hidden]
+                       "--algo", args.algo, "--hidden", args.hidden, "--mb-size", str(args.mb_size)]
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
                 except subprocess.TimeoutExpired:
@@ -146,13 +152,13 @@ def main():
                 out = json.loads(r.stdout.strip().splitlines()[-1])
                 if not out["finite"]:
                     sys.exit("policy_fit_bench: the %s run left non-finite parameters; stopping" % backend)
-                steps, norm[backend], hidden = out["steps"], out["param_norm"], out["hidden"]
+                steps, norm[backend], hidden, mb = out["steps"], out["param_norm"], out["hidden"], out["mb_size"]
                 if pair > 0:   # pair 0 is the warm-up pair
                     runs[backend].append((out["call_s"], out["epochs_s"]))
 
         def summary(xs):
             return dict(median=statistics.median(xs), min=min(xs), max=max(xs), runs=xs)
-        one = dict(steps=steps, hidden=hidden, param_norm=norm)
+        one = dict(steps=steps, hidden=hidden, mb_size=mb, param_norm=norm)
         for k in pair_of:
             one[k + "_call_s"] = summary([c for c, _ in runs[k]])
             one[k + "_epochs_s"] = summary([e for _, e in runs[k]])
