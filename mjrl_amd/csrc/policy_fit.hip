@@ -2,7 +2,7 @@
 // as one hand-written kernel (mjrl/algos/ppo_clip.py:47-54,
 // 89-95, behavior_cloning.py:39-63), for 1 <= h0, h1, m <= 64 (actual sizes: zero-padded in
 // the loads, not in memory).  The policy, the masking of rows, the heads (k_pfit<true>: MSE) and
-// every piece this kernel shares with policy_fit_wide.hip are policy_step.h's.
+// every piece this kernel shares with policy_fit_wide.hip and policy_fit_rows.hip are policy_step.h's.
 //
 //   k_pfit   ONE workgroup of 8 waves owns the whole chain of steps: a launch runs up
 //       to PF_SPL consecutive steps in a loop.  The steps are serially dependent, so
@@ -14,21 +14,22 @@
 //       optimizer's own tensors, L2-resident); __syncthreads() separates a step's
 //       stores from the next step's loads (workgroup scope is enough on one CU).
 //
-// A step, every phase ending in a workgroup barrier (in brackets: policy_step.h's piece):
+// A step, every phase ending in a workgroup barrier (in brackets: policy_step.h's piece; k_pfr_grad
+// of policy_fit_rows.hip runs the same pieces on a row tile, the wide kernels those that fit them):
 //   1  row indices (mb_row), per-column constants (head_consts)
-//   2  layer 0 over column chunks of the gathered, normalised X tile (stage_x, 256 columns
-//      in LDS at a time): a0 = tanh(xhat W0^T + b0)
-//   3  a1 = tanh(a0 W1^T + b1)
-//   4  mu = (a1 W2^T + b2) out_scale + out_shift, z = (act - mu) / sigma (head_z)
+//   2  layer 0 over column chunks of the gathered, normalised X tile (chain_fwd_x over stage_x,
+//      256 columns in LDS at a time): a0 = tanh(xhat W0^T + b0) (chain_tanh)
+//   3  a1 = tanh(a0 W1^T + b1) (chain_fwd, chain_tanh)
+//   4  mu = (a1 W2^T + b2) out_scale + out_shift, z = (act - mu) / sigma (chain_fwd, head_z)
 //   5  per row: LL, the loss head, dL/dLL (head_rows)
-//   6  d log_std, the step's loss (head_sums); then gmu in place of z (head_gmu)
-//   7  g1 = (gmu W2) o (1 - a1^2)
-//   8  g0 = (g1 W1) o (1 - a0^2)
-//   9  the weight gradients as 16 x 16 jobs (wgrad_job: dW2 = gmu^T [a1, 1], dW1 = g1^T [a0, 1],
-//      dW0 = g0^T [xhat, 1] chunk by chunk, the last forward chunk first: it is still
-//      in LDS; the bias sums ride along as a column of ones), Adam on exactly the
-//      elements of each job, log_std's Adam.  Every use of a step's parameters is
-//      behind a barrier before the first of these stores.
+//   6  d log_std, the step's loss (head_sums over head_dls); then gmu in place of z (head_gmu)
+//   7  g1 = (gmu W2) o (1 - a1^2) (chain_bwd)
+//   8  g0 = (g1 W1) o (1 - a0^2) (chain_bwd)
+//   9  the weight gradients as 16 x 16 jobs (wgrad_walk over wgrad_job: dW2 = gmu^T [a1, 1],
+//      dW1 = g1^T [a0, 1], dW0 = g0^T [xhat, 1] chunk by chunk, the last forward chunk first: it
+//      is still in LDS; the bias sums ride along as a column of ones), Adam on exactly the
+//      elements of each job, log_std's Adam (log_std_adam).  Every use of a step's parameters is
+//      behind a barrier before the first of these stores.  The tensors' places in grad_out: grad_at.
 //
 // Arithmetic: products on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fma chain,
 // one accumulator per output tile), every sum in one fixed order, no atomic: the same
@@ -41,13 +42,8 @@ using namespace mjrl;
 
 namespace {
 
-constexpr int PR = PS_ROWS;           // padded minibatch rows
-constexpr int PH = 64;                // largest hidden / action width
-constexpr int PLD = PH + 4;           // LDS row pitch of the [64][64] tiles: rows 4 banks apart
-constexpr int XCW = PS_XCW;           // columns of the X tile held in LDS at a time
-constexpr int XLD = XCW + 4;          // its row pitch
+constexpr int PR = PS_ROWS, PH = PS_H, PLD = PS_LD, XLD = PS_XLD;   // the tiles: policy_step.h
 constexpr int PF_THREADS = PS_THREADS;
-constexpr int PW = PF_THREADS / 64;   // waves
 constexpr int PF_SPL = 128;           // steps of one launch at the most (their Adam constants are kernel arguments)
 constexpr int64_t PF_SCRATCH = 64;    // floats: [0] the last step's loss
 
@@ -102,17 +98,15 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
     const int MP = 16 * UB2;
     const bool aliased = a.kind == PF_PPO && a.old_ls != nullptr;
     float *const W0 = a.p[0], *const b0 = a.p[1], *const W1 = a.p[2], *const b1 = a.p[3], *const W2 = a.p[4];
-    // flat places of the seven tensors in a step's gradient
-    const int64_t o_b0 = (int64_t)h0 * n, o_W1 = o_b0 + h0, o_b1 = o_W1 + (int64_t)h1 * h0, o_W2 = o_b1 + h1,
-                  o_b2 = o_W2 + (int64_t)m * h1, o_ls = o_b2 + m;
+    const GradAt o = grad_at(n, m, h0, h1, MSE);
+    const ChainTiles tiles = {Xs, a0s, a1s, g0s, g1s, zs};
     // forward / chain products: wave w owns unit block w & 3 and the row blocks 2 (w >> 2), + 1
     const int ub = w & 3, rb0 = 2 * (w >> 2);
-    const int nchunk_f = (n + XCW - 1) / XCW;   // forward chunks
-    const int nchunk_b = n / XCW + 1;           // backward chunks: the column of ones (col n) counts
 
     AdamK hp = a.hp;   // step_size / bc2s: the current step's, set below
     // a lambda capturing n: called directly, stage_x costs 69 more SGPR reloads and 0.4 % of Swimmer's epochs
     const auto load_chunk = [&](int c) { stage_x<XLD>(a, n, s_row, Xs, c, tid); };
+    const auto stamp = [&](int i) { PF_STAMP(i); };
 
     for (int step = 0; step < a.nsteps; ++step) {
         hp.step_size = a.step_size[step];
@@ -130,34 +124,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
         // ---- 2: a0 = tanh(xhat W0^T + b0), xhat chunk by chunk ----
         {
             floatx4 acc[2] = {zero4(), zero4()};
-            for (int c = 0; c < nchunk_f; ++c) {
-                if (c > 0) __syncthreads();   // the previous chunk's products have read Xs
-                load_chunk(c);
-                __syncthreads();
-                PF_STAMP(c == 0 ? 1 : 12);
-                if (ub < UB0) {
-                    const int c0 = c * XCW, cw = n - c0 < XCW ? n - c0 : XCW, ng = (cw + 15) / 16;
-#pragma unroll 4
-                    for (int g = 0; g < ng; ++g) {
-                        const float4 b = ldw4(W0, h0, n, 16 * ub + r, c0 + 16 * g + 4 * q, a.vw0);
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const float4 av =
-                                *reinterpret_cast<const float4*>(Xs + (16 * (rb0 + i) + r) * XLD + 16 * g + 4 * q);
-                            acc[i] = mfma_k16(av, b, acc[i]);
-                        }
-                    }
-                }
-            }
-            if (ub < UB0) {
-                const int col = 16 * ub + r;
-                const float bias = col < h0 ? b0[col] : 0.f;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        a0s[(16 * (rb0 + i) + 4 * q + k) * PLD + col] = col < h0 ? tanhf(acc[i][k] + bias) : 0.f;
-            }
+            chain_fwd_x<XLD, 2>(acc, Xs, ub < UB0, rb0, W0, h0, n, ub, a.vw0, r, q, load_chunk, stamp);
+            if (ub < UB0) chain_tanh<PLD>(acc, a0s, rb0, b0, h0, ub, r, q);
         }
         __syncthreads();
         PF_STAMP(2);
@@ -165,22 +133,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
         // ---- 3: a1 = tanh(a0 W1^T + b1) ----
         if (ub < UB1) {
             floatx4 acc[2] = {zero4(), zero4()};
-#pragma unroll 4
-            for (int g = 0; g < UB0; ++g) {
-                const float4 b = ldw4(W1, h1, h0, 16 * ub + r, 16 * g + 4 * q, a.vw1);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float4 av = *reinterpret_cast<const float4*>(a0s + (16 * (rb0 + i) + r) * PLD + 16 * g + 4 * q);
-                    acc[i] = mfma_k16(av, b, acc[i]);
-                }
-            }
-            const int col = 16 * ub + r;
-            const float bias = col < h1 ? b1[col] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    a1s[(16 * (rb0 + i) + 4 * q + k) * PLD + col] = col < h1 ? tanhf(acc[i][k] + bias) : 0.f;
+            chain_fwd<PLD, 2>(acc, a0s, rb0, W1, h1, h0, ub, 0, UB0, a.vw1, r, q);
+            chain_tanh<PLD>(acc, a1s, rb0, b1, h1, ub, r, q);
         }
         __syncthreads();
         PF_STAMP(3);
@@ -188,15 +142,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
         // ---- 4: mu = (a1 W2^T + b2) out_scale + out_shift, z = (act - mu) / sigma ----
         if (ub < UB2) {
             floatx4 acc[2] = {zero4(), zero4()};
-#pragma unroll 4
-            for (int g = 0; g < UB1; ++g) {
-                const float4 b = ldw4(W2, m, h1, 16 * ub + r, 16 * g + 4 * q, a.vw2);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float4 av = *reinterpret_cast<const float4*>(a1s + (16 * (rb0 + i) + r) * PLD + 16 * g + 4 * q);
-                    acc[i] = mfma_k16(av, b, acc[i]);
-                }
-            }
+            chain_fwd<PLD, 2>(acc, a1s, rb0, W2, m, h1, ub, 0, UB1, a.vw2, r, q);
             head_z<MSE, PLD>(a, acc, ub, rb0, r, q, s_sig, s_row, zs);
         }
         __syncthreads();
@@ -215,90 +161,22 @@ __global__ void __launch_bounds__(PF_THREADS) k_pfit(PfitArgs a) {
         PF_STAMP(6);
 
         // ---- 7: g1 = (gmu W2) o (1 - a1^2) ----
-        if (ub < UB1) {
-            floatx4 acc[2] = {zero4(), zero4()};
-            const int col = 16 * ub + r;
-            for (int g = 0; g < UB2; ++g) {
-                const int j = 16 * g + 4 * q;
-                const float4 b = ldwt4(W2, m, h1, j, col);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float4 av = *reinterpret_cast<const float4*>(zs + (16 * (rb0 + i) + r) * PLD + j);
-                    acc[i] = mfma_k16(av, b, acc[i]);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int row = 16 * (rb0 + i) + 4 * q + k;
-                    const float av = a1s[row * PLD + col];
-                    g1s[row * PLD + col] = col < h1 ? acc[i][k] * (1.f - av * av) : 0.f;
-                }
-        }
+        if (ub < UB1) chain_bwd<PLD>(zs, W2, m, h1, UB2, a1s, g1s, ub, rb0, r, q);
         __syncthreads();
         PF_STAMP(7);
 
         // ---- 8: g0 = (g1 W1) o (1 - a0^2) ----
-        if (ub < UB0) {
-            floatx4 acc[2] = {zero4(), zero4()};
-            const int col = 16 * ub + r;
-            for (int g = 0; g < UB1; ++g) {
-                const int j = 16 * g + 4 * q;
-                const float4 b = ldwt4(W1, h1, h0, j, col);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const float4 av = *reinterpret_cast<const float4*>(g1s + (16 * (rb0 + i) + r) * PLD + j);
-                    acc[i] = mfma_k16(av, b, acc[i]);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int row = 16 * (rb0 + i) + 4 * q + k;
-                    const float av = a0s[row * PLD + col];
-                    g0s[row * PLD + col] = col < h0 ? acc[i][k] * (1.f - av * av) : 0.f;
-                }
-        }
+        if (ub < UB0) chain_bwd<PLD>(g1s, W1, h1, h0, UB1, a0s, g0s, ub, rb0, r, q);
         __syncthreads();
         PF_STAMP(8);
 
         // ---- 9: the weight gradients and Adam; every read of this step's parameters is behind us ----
-        if (!MSE && w == 0 && lane < m) log_std_adam(a, hp, dls, lane, grad, o_ls);
-        {
-            // the units 16 jub .. + 15 of a layer (upstream tile gl, pitch PLD) against 16 columns of [input, 1]
-            const auto job = [&](int t, int U, int K, int jub, int col0, const float* gl, const float* bl, int bld,
-                                 int boff, int64_t gw, int64_t gb) {
-                wgrad_job(a, hp, grad, t, U, K, jub, col0, gl, PLD, 16 * jub, bl, bld, boff, gw, gb, r, q);
-            };
-            const int CB2 = h1 / 16 + 1, CB1 = h0 / 16 + 1;   // column blocks of [a1, 1], [a0, 1]
-            const int nj2 = UB2 * CB2, nj1 = UB1 * CB1;
-            int resident = nchunk_f - 1;
-            for (int c = nchunk_b - 1; c >= 0; --c) {
-                if (c != resident && n > c * XCW) {   // (a chunk holding only the column of ones needs no tile)
-                    PF_STAMP(10);
-                    __syncthreads();   // the previous chunk's jobs have read Xs
-                    PF_STAMP(13);
-                    load_chunk(c);
-                    __syncthreads();
-                    resident = c;
-                    PF_STAMP(9);
-                }
-                const int cb0 = n / 16 + 1 - c * (XCW / 16);          // layer 0's column blocks from this chunk on
-                const int nb0 = cb0 < XCW / 16 ? cb0 : XCW / 16;
-                const int nj0 = UB0 * nb0;
-                const int nj = nj0 + (c == nchunk_b - 1 ? nj2 + nj1 : 0);   // the first chunk visited carries layers 2 and 1
-                for (int j = w; j < nj; j += PW) {
-                    if (j < nj0)
-                        job(0, h0, n, j / nb0, c * XCW + 16 * (j % nb0), g0s, Xs, XLD, c * XCW, 0, o_b0);
-                    else if (j < nj0 + nj2)
-                        job(4, m, h1, (j - nj0) / CB2, 16 * ((j - nj0) % CB2), zs, a1s, PLD, 0, o_W2, o_b2);
-                    else
-                        job(2, h1, h0, (j - nj0 - nj2) / CB1, 16 * ((j - nj0 - nj2) % CB1), g1s, a0s, PLD, 0, o_W1, o_b1);
-                }
-            }
-        }
+        if (!MSE && w == 0 && lane < m) log_std_adam(a, hp, dls, lane, grad, o.ls);
+        const auto job = [&](int t, int U, int K, int jub, int col0, const float* gl, const float* bl, int bld,
+                             int boff, int64_t gw, int64_t gb) {
+            wgrad_job(a, hp, grad, t, U, K, jub, col0, gl, PLD, 16 * jub, bl, bld, boff, gw, gb, r, q);
+        };
+        wgrad_walk(n, m, h0, h1, w, tiles, o, load_chunk, job, stamp);
         PF_STAMP(10);      // wave 0's own jobs
         __syncthreads();   // this step's stores before the next step's loads (one CU: workgroup scope)
         PF_STAMP(11);

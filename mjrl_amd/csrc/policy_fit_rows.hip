@@ -1,8 +1,8 @@
 // policy_fit_rows.hip — policy_fit.hip's minibatch Adam step (phases 1-9 of its header comment)
 // for minibatches of up to 16384 rows, sliced over row tiles (fit_backend = "hip_rows";
 // mjrl_policy_fit_rows_epoch), for 1 <= h0, h1, m <= 64 and the BC and PPO heads (the MSE head is
-// not built here).  The policy, the masking of rows, the heads and the weight-gradient product
-// are policy_step.h's.
+// not built here).  The policy, the masking of rows, the heads, the chain products of phases 2-8
+// and phase 9's walk over the weight-gradient jobs are policy_step.h's, as they are k_pfit's.
 //
 // The forward chain, the loss head and the backward chain of 64 rows are independent of every
 // other 64 rows; only the weight-gradient sums and Adam join them.  So one workgroup owns 64 rows
@@ -27,9 +27,6 @@
 // The scratch (floats): [0] the last step's loss, [4 .. 516) the 256 tiles' loss sums as doubles,
 // from 516 on the slab.
 //
-// k_pfr_grad's phases 2-8 are a copy of k_pfit's (about 130 lines): that kernel is at its register
-// limit and stays as it is; one body under the three files is a later change.
-//
 // Arithmetic: policy_fit.hip's contract (exact-f32 MFMA, one accumulator per output tile, k
 // ascending, every sum in one fixed order, no atomic, fit.h's Adam, the bias corrections formed
 // on the host): the same state and arguments give the same bits, however the steps are split
@@ -40,13 +37,8 @@ using namespace mjrl;
 
 namespace {
 
-constexpr int PR = PS_ROWS;           // rows of a tile
-constexpr int PH = 64;                // largest hidden / action width
-constexpr int PLD = PH + 4;           // LDS row pitch of the [64][64] tiles: rows 4 banks apart
-constexpr int XCW = PS_XCW;           // columns of the X tile held in LDS at a time
-constexpr int XLD = XCW + 4;          // its row pitch
+constexpr int PR = PS_ROWS, PH = PS_H, PLD = PS_LD, XLD = PS_XLD;   // the tiles: policy_step.h
 constexpr int RT = PS_THREADS;        // threads of a k_pfr_grad workgroup
-constexpr int PW = RT / 64;           // its waves
 constexpr int MAX_TILES = MJRL_POLICY_FIT_ROWS_MAX_BS / PR;
 constexpr int AT = 256;               // threads of a k_pfr_adam workgroup
 constexpr int LOSS_OFF = 0, LSUM_OFF = 4, SLAB_OFF = LSUM_OFF + 2 * MAX_TILES;   // floats; 16-byte aligned
@@ -80,16 +72,14 @@ __global__ void __launch_bounds__(RT) k_pfr_grad(RowsArgs a) {
     const int MP = 16 * UB2;
     const bool aliased = a.kind == PF_PPO && a.old_ls != nullptr;
     const float *const W0 = a.p[0], *const b0 = a.p[1], *const W1 = a.p[2], *const b1 = a.p[3], *const W2 = a.p[4];
-    // flat places of the seven tensors in a step's gradient
-    const int64_t o_b0 = (int64_t)h0 * n, o_W1 = o_b0 + h0, o_b1 = o_W1 + (int64_t)h1 * h0, o_W2 = o_b1 + h1,
-                  o_b2 = o_W2 + (int64_t)m * h1, o_ls = o_b2 + m;
+    const GradAt o = grad_at(n, m, h0, h1, false);
+    const ChainTiles tiles = {Xs, a0s, a1s, g0s, g1s, zs};
     const int64_t off = SLAB_OFF + (int64_t)tile * a.d;   // this tile's slice of the slab
     // forward / chain products: wave w owns unit block w & 3 and the row blocks 2 (w >> 2), + 1
     const int ub = w & 3, rb0 = 2 * (w >> 2);
-    const int nchunk_f = (n + XCW - 1) / XCW;   // forward chunks
-    const int nchunk_b = n / XCW + 1;           // backward chunks: the column of ones (col n) counts
 
     const auto load_chunk = [&](int c) { stage_x<XLD>(a, n, s_row, Xs, c, tid); };
+    const auto no_stamp = [](int) {};
 
     // ---- 1: the row indices, the per-column constants ----
     if (w == 0)
@@ -101,70 +91,23 @@ __global__ void __launch_bounds__(RT) k_pfr_grad(RowsArgs a) {
     // ---- 2: a0 = tanh(xhat W0^T + b0), xhat chunk by chunk ----
     {
         floatx4 acc[2] = {zero4(), zero4()};
-        for (int c = 0; c < nchunk_f; ++c) {
-            if (c > 0) __syncthreads();   // the previous chunk's products have read Xs
-            load_chunk(c);
-            __syncthreads();
-            if (ub < UB0) {
-                const int c0 = c * XCW, cw = n - c0 < XCW ? n - c0 : XCW, ng = (cw + 15) / 16;
-#pragma unroll 4
-                for (int g = 0; g < ng; ++g) {
-                    const float4 b = ldw4(W0, h0, n, 16 * ub + r, c0 + 16 * g + 4 * q, a.vw0);
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const float4 av =
-                            *reinterpret_cast<const float4*>(Xs + (16 * (rb0 + i) + r) * XLD + 16 * g + 4 * q);
-                        acc[i] = mfma_k16(av, b, acc[i]);
-                    }
-                }
-            }
-        }
-        if (ub < UB0) {
-            const int col = 16 * ub + r;
-            const float bias = col < h0 ? b0[col] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    a0s[(16 * (rb0 + i) + 4 * q + k) * PLD + col] = col < h0 ? tanhf(acc[i][k] + bias) : 0.f;
-        }
+        chain_fwd_x<XLD, 2>(acc, Xs, ub < UB0, rb0, W0, h0, n, ub, a.vw0, r, q, load_chunk, no_stamp);
+        if (ub < UB0) chain_tanh<PLD>(acc, a0s, rb0, b0, h0, ub, r, q);
     }
     __syncthreads();
 
     // ---- 3: a1 = tanh(a0 W1^T + b1) ----
     if (ub < UB1) {
         floatx4 acc[2] = {zero4(), zero4()};
-#pragma unroll 4
-        for (int g = 0; g < UB0; ++g) {
-            const float4 b = ldw4(W1, h1, h0, 16 * ub + r, 16 * g + 4 * q, a.vw1);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4 av = *reinterpret_cast<const float4*>(a0s + (16 * (rb0 + i) + r) * PLD + 16 * g + 4 * q);
-                acc[i] = mfma_k16(av, b, acc[i]);
-            }
-        }
-        const int col = 16 * ub + r;
-        const float bias = col < h1 ? b1[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                a1s[(16 * (rb0 + i) + 4 * q + k) * PLD + col] = col < h1 ? tanhf(acc[i][k] + bias) : 0.f;
+        chain_fwd<PLD, 2>(acc, a0s, rb0, W1, h1, h0, ub, 0, UB0, a.vw1, r, q);
+        chain_tanh<PLD>(acc, a1s, rb0, b1, h1, ub, r, q);
     }
     __syncthreads();
 
     // ---- 4: mu = (a1 W2^T + b2) out_scale + out_shift, z = (act - mu) / sigma ----
     if (ub < UB2) {
         floatx4 acc[2] = {zero4(), zero4()};
-#pragma unroll 4
-        for (int g = 0; g < UB1; ++g) {
-            const float4 b = ldw4(W2, m, h1, 16 * ub + r, 16 * g + 4 * q, a.vw2);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4 av = *reinterpret_cast<const float4*>(a1s + (16 * (rb0 + i) + r) * PLD + 16 * g + 4 * q);
-                acc[i] = mfma_k16(av, b, acc[i]);
-            }
-        }
+        chain_fwd<PLD, 2>(acc, a1s, rb0, W2, m, h1, ub, 0, UB1, a.vw2, r, q);
         head_z<false, PLD>(a, acc, ub, rb0, r, q, s_sig, s_row, zs);
     }
     __syncthreads();
@@ -173,17 +116,10 @@ __global__ void __launch_bounds__(RT) k_pfr_grad(RowsArgs a) {
     head_rows<false, PLD>(a, aliased, tid, zs, s_q, s_lsum, s_row, s_gll, s_lossd);
     __syncthreads();
 
-    // ---- 6: the tile's d log_std (wave 0, head_sums' sum) and loss sum (wave 1); then gmu in place of z ----
+    // ---- 6: the tile's d log_std (wave 0) and loss sum (wave 1); then gmu in place of z ----
     float dls = 0.f;
     if (w == 0) {
-        if (lane < m) {
-            double s = 0.0;
-            for (int row = 0; row < PR; ++row) {
-                const double z = (double)zs[row * PLD + lane];
-                s += (double)s_gll[row] * (z * z - 1.0);
-            }
-            dls = (float)s;
-        }
+        dls = head_dls<PLD>(m, lane, zs, s_gll);
     } else if (w == 1) {
         const double tot = wave_sum(s_lossd[lane]);
         if (lane == 0) {
@@ -196,86 +132,23 @@ __global__ void __launch_bounds__(RT) k_pfr_grad(RowsArgs a) {
     __syncthreads();
 
     // ---- 7: g1 = (gmu W2) o (1 - a1^2) ----
-    if (ub < UB1) {
-        floatx4 acc[2] = {zero4(), zero4()};
-        const int col = 16 * ub + r;
-        for (int g = 0; g < UB2; ++g) {
-            const int j = 16 * g + 4 * q;
-            const float4 b = ldwt4(W2, m, h1, j, col);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4 av = *reinterpret_cast<const float4*>(zs + (16 * (rb0 + i) + r) * PLD + j);
-                acc[i] = mfma_k16(av, b, acc[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int row = 16 * (rb0 + i) + 4 * q + k;
-                const float av = a1s[row * PLD + col];
-                g1s[row * PLD + col] = col < h1 ? acc[i][k] * (1.f - av * av) : 0.f;
-            }
-    }
+    if (ub < UB1) chain_bwd<PLD>(zs, W2, m, h1, UB2, a1s, g1s, ub, rb0, r, q);
     __syncthreads();
 
     // ---- 8: g0 = (g1 W1) o (1 - a0^2) ----
-    if (ub < UB0) {
-        floatx4 acc[2] = {zero4(), zero4()};
-        const int col = 16 * ub + r;
-        for (int g = 0; g < UB1; ++g) {
-            const int j = 16 * g + 4 * q;
-            const float4 b = ldwt4(W1, h1, h0, j, col);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4 av = *reinterpret_cast<const float4*>(g1s + (16 * (rb0 + i) + r) * PLD + j);
-                acc[i] = mfma_k16(av, b, acc[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int row = 16 * (rb0 + i) + 4 * q + k;
-                const float av = a0s[row * PLD + col];
-                g0s[row * PLD + col] = col < h0 ? acc[i][k] * (1.f - av * av) : 0.f;
-            }
-    }
+    if (ub < UB0) chain_bwd<PLD>(g1s, W1, h1, h0, UB1, a0s, g0s, ub, rb0, r, q);
     __syncthreads();
 
     // ---- 9: the tile's weight gradients into its slice, k_pfit's jobs in k_pfit's order ----
     if (w == 0 && lane < m) {
-        MJRL_SLAB_CHECK(off + o_ls + lane, a.scap);
-        a.scratch[off + o_ls + lane] = dls;
+        MJRL_SLAB_CHECK(off + o.ls + lane, a.scap);
+        a.scratch[off + o.ls + lane] = dls;
     }
-    // the units 16 jub .. + 15 of a layer (upstream tile gl, pitch PLD) against 16 columns of [input, 1]
-    const auto job = [&](int U, int K, int jub, int col0, const float* gl, const float* bl, int bld, int boff,
+    const auto job = [&](int, int U, int K, int jub, int col0, const float* gl, const float* bl, int bld, int boff,
                          int64_t gw, int64_t gb) {
         wgrad_store_job(a, off, U, K, jub, col0, gl, PLD, 16 * jub, bl, bld, boff, gw, gb, r, q);
     };
-    const int CB2 = h1 / 16 + 1, CB1 = h0 / 16 + 1;   // column blocks of [a1, 1], [a0, 1]
-    const int nj2 = UB2 * CB2, nj1 = UB1 * CB1;
-    int resident = nchunk_f - 1;
-    for (int c = nchunk_b - 1; c >= 0; --c) {
-        if (c != resident && n > c * XCW) {   // (a chunk holding only the column of ones needs no tile)
-            __syncthreads();   // the previous chunk's jobs have read Xs
-            load_chunk(c);
-            __syncthreads();
-            resident = c;
-        }
-        const int cb0 = n / 16 + 1 - c * (XCW / 16);          // layer 0's column blocks from this chunk on
-        const int nb0 = cb0 < XCW / 16 ? cb0 : XCW / 16;
-        const int nj0 = UB0 * nb0;
-        const int nj = nj0 + (c == nchunk_b - 1 ? nj2 + nj1 : 0);   // the first chunk visited carries layers 2 and 1
-        for (int j = w; j < nj; j += PW) {
-            if (j < nj0)
-                job(h0, n, j / nb0, c * XCW + 16 * (j % nb0), g0s, Xs, XLD, c * XCW, 0, o_b0);
-            else if (j < nj0 + nj2)
-                job(m, h1, (j - nj0) / CB2, 16 * ((j - nj0) % CB2), zs, a1s, PLD, 0, o_W2, o_b2);
-            else
-                job(h1, h0, (j - nj0 - nj2) / CB1, 16 * ((j - nj0 - nj2) % CB1), g1s, a0s, PLD, 0, o_W1, o_b1);
-        }
-    }
+    wgrad_walk(n, m, h0, h1, w, tiles, o, load_chunk, job, no_stamp);
 }
 
 // The fold over the row tiles and Adam: workgroups 0 .. ceil(d / AT) - 1 own AT elements each of
@@ -311,11 +184,10 @@ __global__ void __launch_bounds__(AT) k_pfr_adam(RowsArgs a) {
     for (int g = 1; g < G; ++g) s += (double)part[(int64_t)g * d];
     const float gr = (float)s;
     // the element's tensor and its place in it (torch parameter order)
-    const int n = a.n, m = a.na, h0 = a.h0, h1 = a.h1;
-    const int64_t o1 = (int64_t)h0 * n, o2 = o1 + h0, o3 = o2 + (int64_t)h1 * h0, o4 = o3 + h1,
-                  o5 = o4 + (int64_t)m * h1, o6 = o5 + m;
-    const int t = (e >= o1) + (e >= o2) + (e >= o3) + (e >= o4) + (e >= o5) + (e >= o6);
-    const int64_t i = e - (t == 0 ? 0 : t == 1 ? o1 : t == 2 ? o2 : t == 3 ? o3 : t == 4 ? o4 : t == 5 ? o5 : o6);
+    const GradAt o = grad_at(a.n, a.na, a.h0, a.h1, false);
+    const int t = (e >= o.b0) + (e >= o.W1) + (e >= o.b1) + (e >= o.W2) + (e >= o.b2) + (e >= o.ls);
+    const int64_t i =
+        e - (t == 0 ? 0 : t == 1 ? o.b0 : t == 2 ? o.W1 : t == 3 ? o.b1 : t == 4 ? o.W2 : t == 5 ? o.b2 : o.ls);
     const auto pick = [t](float* (&x)[7]) {
         return t == 0 ? x[0] : t == 1 ? x[1] : t == 2 ? x[2] : t == 3 ? x[3] : t == 4 ? x[4] : t == 5 ? x[5] : x[6];
     };
@@ -333,9 +205,9 @@ __global__ void __launch_bounds__(AT) k_pfr_adam(RowsArgs a) {
 extern "C" {
 
 int mjrl_policy_fit_rows_scratch(int32_t n, int32_t m, int32_t h0, int32_t h1, int32_t bs, int64_t* floats) {
-    const int64_t d = (int64_t)h0 * n + h0 + (int64_t)h1 * h0 + h1 + (int64_t)m * h1 + m + m;
     const int64_t G = ((int64_t)bs + PR - 1) / PR;
-    return scratch_query(n, m, h0, h1, bs, PH, rows_scratch(d, G), floats, MJRL_POLICY_FIT_ROWS_MAX_BS);
+    return scratch_query(n, m, h0, h1, bs, PH, rows_scratch(grad_at(n, m, h0, h1, false).d, G), floats,
+                         MJRL_POLICY_FIT_ROWS_MAX_BS);
 }
 
 int mjrl_policy_fit_rows_epoch(const mjrl_policy_fit_data* data, const int64_t* idx, int64_t nmb, int32_t bs,

@@ -94,14 +94,8 @@ __global__ void __launch_bounds__(WT) k_wide_l0(WideArgs a) {
         __syncthreads();
         if (w < 4) {
             const int col = 16 * u + r;
-            floatx4 acc = zero4();
-#pragma unroll 4
-            for (int g = 0; g < UB1; ++g) {
-                const int j = 16 * g + 4 * q;
-                const float4 b = ldwt4(W1, h1, h0, j, col);
-                const float4 av = *reinterpret_cast<const float4*>(Ts + (16 * w + r) * TLD + j);
-                acc = mfma_k16(av, b, acc);
-            }
+            floatx4 acc[1] = {zero4()};
+            chain_bwd_prod<TLD, 1>(acc, Ts, w, W1, h1, h0, col, UB1, r, q);
             const float* const a0u = a.scratch + a0_off(a.kU);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -110,13 +104,13 @@ __global__ void __launch_bounds__(WT) k_wide_l0(WideArgs a) {
                 if (col < h0) {
                     MJRL_SLAB_CHECK(a0_off(a.kU) + row * WP + col, a.scap);
                     const float av = a0u[row * WP + col];
-                    gv = acc[k] * (1.f - av * av);
+                    gv = acc[0][k] * (1.f - av * av);
                 }
                 gs[row * 16 + r] = gv;
             }
         }
         // dW0 / db0 of the units 16 u .. + 15 and Adam, one 16-column block of [xhat, 1] a job
-        const int64_t o_b0 = (int64_t)h0 * n;
+        const int64_t o_b0 = grad_at(n, a.na, h0, h1, false).b0;
         const int cb0 = n / 16 + 1, nchunk = n / XCW + 1;   // the column of ones (col n) counts
         for (int c = 0; c < nchunk; ++c) {
             __syncthreads();   // the products before have read Ts (and written gs)
@@ -132,22 +126,10 @@ __global__ void __launch_bounds__(WT) k_wide_l0(WideArgs a) {
 
     if (a.forward) {
         __syncthreads();   // W0 / b0 as this workgroup's waves have just written them; Ts is free; s_rf
-        floatx4 acc = zero4();
-        const int nchunk = (n + XCW - 1) / XCW;
-        for (int c = 0; c < nchunk; ++c) {
-            if (c > 0) __syncthreads();
-            stage_x<TLD>(a, n, s_rf, Ts, c, tid);
-            __syncthreads();
-            if (w < 4) {
-                const int c0 = c * XCW, cw = n - c0 < XCW ? n - c0 : XCW, ng = (cw + 15) / 16;
-#pragma unroll 4
-                for (int g = 0; g < ng; ++g) {
-                    const float4 b = ldw4(W0, h0, n, 16 * u + r, c0 + 16 * g + 4 * q, a.vw0);
-                    const float4 av = *reinterpret_cast<const float4*>(Ts + (16 * w + r) * TLD + 16 * g + 4 * q);
-                    acc = mfma_k16(av, b, acc);
-                }
-            }
-        }
+        floatx4 acc[1] = {zero4()};   // rows 16 w .. + 15 by wave w < 4
+        chain_fwd_x<TLD, 1>(
+            acc, Ts, w < 4, w, W0, h0, n, u, a.vw0, r, q, [&](int c) { stage_x<TLD>(a, n, s_rf, Ts, c, tid); },
+            [](int) {});
         if (w < 4) {
             const int col = 16 * u + r;
             const float bias = col < h0 ? b0[col] : 0.f;
@@ -156,7 +138,7 @@ __global__ void __launch_bounds__(WT) k_wide_l0(WideArgs a) {
             for (int k = 0; k < 4; ++k) {
                 const int row = 16 * w + 4 * q + k;
                 MJRL_SLAB_CHECK(a0_off(a.kF) + row * WP + col, a.scap);
-                a0f[row * WP + col] = col < h0 ? tanhf(acc[k] + bias) : 0.f;
+                a0f[row * WP + col] = col < h0 ? tanhf(acc[0][k] + bias) : 0.f;
             }
         }
     }
@@ -180,10 +162,10 @@ __global__ void __launch_bounds__(WT) k_wide_l1(WideArgs a) {
             gs[e] = a.scratch[G1_OFF + (e >> 4) * WP + 16 * u + (e & 15)];
         }
         __syncthreads();
-        const int64_t o_W1 = (int64_t)h0 * n + h0, o_b1 = o_W1 + (int64_t)h1 * h0;
+        const GradAt o = grad_at(n, a.na, h0, h1, false);
         const int CB1 = h0 / 16 + 1;   // column blocks of [a0, 1]
         for (int j = w; j < CB1; j += WW)
-            wgrad_job(a, a.hp, a.grad, 2, h1, h0, u, 16 * j, gs, 16, 0, As, TLD, 0, o_W1, o_b1, r, q);
+            wgrad_job(a, a.hp, a.grad, 2, h1, h0, u, 16 * j, gs, 16, 0, As, TLD, 0, o.W1, o.b1, r, q);
     }
 
     if (a.forward) {
@@ -191,20 +173,15 @@ __global__ void __launch_bounds__(WT) k_wide_l1(WideArgs a) {
         stage_tile(a, a0_off(a.kF), 16 * UB0, As, tid);
         __syncthreads();
         if (w < 4) {
-            floatx4 acc = zero4();
-#pragma unroll 4
-            for (int g = 0; g < UB0; ++g) {
-                const float4 b = ldw4(W1, h1, h0, 16 * u + r, 16 * g + 4 * q, a.vw1);
-                const float4 av = *reinterpret_cast<const float4*>(As + (16 * w + r) * TLD + 16 * g + 4 * q);
-                acc = mfma_k16(av, b, acc);
-            }
+            floatx4 acc[1] = {zero4()};
+            chain_fwd<TLD, 1>(acc, As, w, W1, h1, h0, u, 0, UB0, a.vw1, r, q);
             const int col = 16 * u + r;
             const float bias = col < h1 ? b1[col] : 0.f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int row = 16 * w + 4 * q + k;
                 MJRL_SLAB_CHECK(A1_OFF + row * WP + col, a.scap);
-                a.scratch[A1_OFF + row * WP + col] = col < h1 ? tanhf(acc[k] + bias) : 0.f;
+                a.scratch[A1_OFF + row * WP + col] = col < h1 ? tanhf(acc[0][k] + bias) : 0.f;
             }
         }
     }
@@ -226,8 +203,7 @@ __global__ void __launch_bounds__(WT) k_wide_head(WideArgs a) {
     const int UB1 = (h1 + 15) / 16, UB2 = (m + 15) / 16, MP = 16 * UB2;
     const bool aliased = a.kind == PF_PPO && a.old_ls != nullptr;
     const float* const W2 = a.p[4];
-    const int64_t o_W2 = (int64_t)a.h0 * a.n + a.h0 + (int64_t)h1 * a.h0 + h1, o_b2 = o_W2 + (int64_t)m * h1,
-                  o_ls = o_b2 + m;
+    const GradAt o = grad_at(a.n, m, a.h0, h1, MSE);
     const int ub = w & 3, rb0 = 2 * (w >> 2);   // mu: wave w owns unit block w & 3, row blocks 2 (w >> 2), + 1
 
     // ---- 1: the row indices, the per-column constants; a1 into LDS ----
@@ -241,15 +217,7 @@ __global__ void __launch_bounds__(WT) k_wide_head(WideArgs a) {
     // ---- 4: mu = (a1 W2^T + b2) out_scale + out_shift, z = (act - mu) / sigma ----
     if (ub < UB2) {
         floatx4 acc[2] = {zero4(), zero4()};
-#pragma unroll 4
-        for (int g = 0; g < UB1; ++g) {
-            const float4 b = ldw4(W2, m, h1, 16 * ub + r, 16 * g + 4 * q, a.vw2);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4 av = *reinterpret_cast<const float4*>(a1s + (16 * (rb0 + i) + r) * TLD + 16 * g + 4 * q);
-                acc[i] = mfma_k16(av, b, acc[i]);
-            }
-        }
+        chain_fwd<TLD, 2>(acc, a1s, rb0, W2, m, h1, ub, 0, UB1, a.vw2, r, q);
         head_z<MSE, ZLD>(a, acc, ub, rb0, r, q, s_sig, s_row, zs);
     }
     __syncthreads();
@@ -268,15 +236,7 @@ __global__ void __launch_bounds__(WT) k_wide_head(WideArgs a) {
     for (int ubb = w; ubb < UB1; ubb += WW) {
         floatx4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
         const int col = 16 * ubb + r;
-        for (int g = 0; g < UB2; ++g) {
-            const int j = 16 * g + 4 * q;
-            const float4 b = ldwt4(W2, m, h1, j, col);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 av = *reinterpret_cast<const float4*>(zs + (16 * i + r) * ZLD + j);
-                acc[i] = mfma_k16(av, b, acc[i]);
-            }
-        }
+        chain_bwd_prod<ZLD, 4>(acc, zs, 0, W2, m, h1, col, UB2, r, q);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -290,10 +250,10 @@ __global__ void __launch_bounds__(WT) k_wide_head(WideArgs a) {
     __syncthreads();   // every read of this step's W2 / b2 / log_std is behind us
 
     // ---- 9 (layer 2): dW2 = gmu^T [a1, 1] as 16 x 16 jobs with Adam, log_std's Adam ----
-    if (!MSE && w == 0 && lane < m) log_std_adam(a, a.hp, dls, lane, a.grad, o_ls);
+    if (!MSE && w == 0 && lane < m) log_std_adam(a, a.hp, dls, lane, a.grad, o.ls);
     const int CB2 = h1 / 16 + 1;   // column blocks of [a1, 1]
     for (int j = w; j < UB2 * CB2; j += WW)
-        wgrad_job(a, a.hp, a.grad, 4, m, h1, j / CB2, 16 * (j % CB2), zs, ZLD, 16 * (j / CB2), a1s, TLD, 0, o_W2, o_b2,
+        wgrad_job(a, a.hp, a.grad, 4, m, h1, j / CB2, 16 * (j % CB2), zs, ZLD, 16 * (j / CB2), a1s, TLD, 0, o.W2, o.b2,
                   r, q);
 }
 

@@ -1,8 +1,10 @@
 // policy_step.h — what the fused minibatch Adam fits of the Gaussian MLP policy share
 // (policy_fit.hip: one workgroup, widths up to 64; policy_fit_wide.hip: three kernels a step,
 // widths up to 256; policy_fit_rows.hip: one workgroup per 64 rows of a minibatch of up to 16384,
-// two kernels a step): the argument block, the gathered X tile, the weight-gradient job, the loss
-// heads with log_std's part of the step, and the host's checks and argument filling.
+// two kernels a step): the argument block, the tile constants, the places of the tensors in a flat
+// gradient, the gathered X tile, the chain products (forward, tanh epilogue, backward with its
+// 1 - a^2 epilogue), the weight-gradient product with its two jobs and phase 9's walk over them,
+// the loss heads with log_std's part of the step, and the host's checks and argument filling.
 //
 // The policy is Linear(n, h0) - tanh - Linear(h0, h1) - tanh - Linear(h1, m) plus log_std[m] in
 // torch's layouts and order.  A step trains on bs <= 64 rows named by a device index buffer
@@ -21,6 +23,9 @@ namespace mjrl {
 constexpr int PS_ROWS = 64;           // padded minibatch rows
 constexpr int PS_NA = 64;             // largest action width
 constexpr int PS_XCW = 256;           // columns of the X tile held in LDS at a time
+constexpr int PS_XLD = PS_XCW + 4;    // its row pitch
+constexpr int PS_H = 64;              // largest hidden width of the one-workgroup chains (k_pfit, k_pfr_grad)
+constexpr int PS_LD = PS_H + 4;       // LDS row pitch of their [64][64] tiles: rows 4 banks apart
 constexpr int PS_THREADS = 512;       // threads of every workgroup
 constexpr int PF_BC = 0, PF_PPO = 1;
 constexpr double HALF_LOG_2PI = 0.91893853320467274178;
@@ -42,6 +47,23 @@ struct StepArgs {
     float clip_lo, clip_hi;           // float(1 - c), float(1 + c)
     AdamK hp;                         // the step-independent part (policy_fit) / of the step the launch updates
 };
+
+// The flat places of b0, W1, b1, W2, b2 and log_std in a step's gradient (torch parameter order,
+// W0 at 0) and d, its floats (MSE: no log_std).
+struct GradAt {
+    int64_t b0, W1, b1, W2, b2, ls, d;
+};
+__host__ __device__ __forceinline__ GradAt grad_at(int n, int m, int h0, int h1, bool mse) {
+    GradAt o;
+    o.b0 = (int64_t)h0 * n;
+    o.W1 = o.b0 + h0;
+    o.b1 = o.W1 + (int64_t)h1 * h0;
+    o.W2 = o.b1 + h1;
+    o.b2 = o.W2 + (int64_t)m * h1;
+    o.ls = o.b2 + m;
+    o.d = o.ls + (mse ? 0 : m);
+    return o;
+}
 
 // row index of minibatch k's row r, or -1 for a masked row
 __device__ __forceinline__ int64_t mb_row(const StepArgs& a, int64_t k, int r) {
@@ -95,13 +117,114 @@ __device__ __forceinline__ void stage_x(const StepArgs& a, int n, const int64_t*
     }
 }
 
-// One weight-gradient job of a wave and Adam (hp) on its elements: the 16 units 16 ublk .. + 15
-// of the layer whose weight tensor is t (U units, K inputs) against the 16 columns col0 .. + 15
-// of [input, 1].  gl / gld / goff: the layer's upstream tile, its pitch and the tile column of
-// the job's unit 0; bl / bld / boff: the input tile and the input column of its column 0.  A
+// ---- the chain products: a lane is (r, q) = (lane & 15, lane >> 4) of its wave, which owns the
+// 16 units 16 ub .. + 15 of a layer and the NB row blocks rb0 .. + NB - 1 of 16 rows ----------------
+// acc[i] += A[rows of block rb0 + i][16 g + 4 q ..] . W[unit][k0 + 16 g + 4 q ..] over g = 0 .. ng - 1,
+// k ascending; A: an LDS tile of pitch LD, W: a [U][K] weight tensor, vec: its vw flag
+template <int LD, int NB>
+__device__ __forceinline__ void chain_fwd(floatx4 (&acc)[NB], const float* A, int rb0, const float* W, int U, int K,
+                                          int ub, int k0, int ng, int vec, int r, int q) {
+#pragma unroll 4
+    for (int g = 0; g < ng; ++g) {
+        const float4 b = ldw4(W, U, K, 16 * ub + r, k0 + 16 * g + 4 * q, vec);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const float4 av = *reinterpret_cast<const float4*>(A + (16 * (rb0 + i) + r) * LD + 16 * g + 4 * q);
+            acc[i] = mfma_k16(av, b, acc[i]);
+        }
+    }
+}
+
+// Layer 0's products over the column chunks of the gathered X tile Xs (pitch LD; load(c) stages
+// chunk c, a barrier on either side of it), by the waves that are active; stamp: as in wgrad_walk
+template <int LD, int NB, class Load, class Stamp>
+__device__ __forceinline__ void chain_fwd_x(floatx4 (&acc)[NB], const float* Xs, bool active, int rb0, const float* W0,
+                                            int h0, int n, int ub, int vec, int r, int q, const Load& load,
+                                            const Stamp& stamp) {
+    constexpr int XCW = PS_XCW;
+    const int nchunk_f = (n + XCW - 1) / XCW;
+    for (int c = 0; c < nchunk_f; ++c) {
+        if (c > 0) __syncthreads();   // the previous chunk's products have read Xs
+        load(c);
+        __syncthreads();
+        stamp(c == 0 ? 1 : 12);
+        if (active) {
+            const int c0 = c * XCW, cw = n - c0 < XCW ? n - c0 : XCW;
+            chain_fwd<LD, NB>(acc, Xs, rb0, W0, h0, n, ub, c0, (cw + 15) / 16, vec, r, q);
+        }
+    }
+}
+
+// tanh(acc + b) of the wave's two row blocks into the LDS tile dst (pitch LD), 0 in the columns from U on
+template <int LD>
+__device__ __forceinline__ void chain_tanh(const floatx4 (&acc)[2], float* dst, int rb0, const float* b, int U, int ub,
+                                           int r, int q) {
+    const int col = 16 * ub + r;
+    const float bias = col < U ? b[col] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            dst[(16 * (rb0 + i) + 4 * q + k) * LD + col] = col < U ? tanhf(acc[i][k] + bias) : 0.f;
+}
+
+// acc[i] += G[rows of block rb0 + i][16 g + 4 q ..] . W[16 g + 4 q ..][col] over g = 0 .. ng - 1: the
+// upstream LDS tile G (pitch LD) through the transpose of the [U][K] weight tensor W
+template <int LD, int NB>
+__device__ __forceinline__ void chain_bwd_prod(floatx4 (&acc)[NB], const float* G, int rb0, const float* W, int U,
+                                               int K, int col, int ng, int r, int q) {
+    for (int g = 0; g < ng; ++g) {
+        const int j = 16 * g + 4 * q;
+        const float4 b = ldwt4(W, U, K, j, col);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const float4 av = *reinterpret_cast<const float4*>(G + (16 * (rb0 + i) + r) * LD + j);
+            acc[i] = mfma_k16(av, b, acc[i]);
+        }
+    }
+}
+
+// dst = (G W) o (1 - act^2) for the wave's unit block of the K inputs of W and its two row blocks;
+// G, act, dst: LDS tiles of pitch LD
+template <int LD>
+__device__ __forceinline__ void chain_bwd(const float* G, const float* W, int U, int K, int ng, const float* act,
+                                          float* dst, int ub, int rb0, int r, int q) {
+    floatx4 acc[2] = {zero4(), zero4()};
+    const int col = 16 * ub + r;
+    chain_bwd_prod<LD, 2>(acc, G, rb0, W, U, K, col, ng, r, q);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int row = 16 * (rb0 + i) + 4 * q + k;
+            const float av = act[row * LD + col];
+            dst[row * LD + col] = col < K ? acc[i][k] * (1.f - av * av) : 0.f;
+        }
+}
+
+// ---- the weight gradients ------------------------------------------------------------------------
+// The product of one weight-gradient job of a wave: the 16 units of a layer (K inputs) at the tile
+// columns goff .. + 15 of the upstream tile gl (pitch gld) against the columns col - r .. + 15 of
+// [input, 1]; bl / bld / boff: the input tile, its pitch and the input column of its column 0.  A
 // lane's accumulator register i belongs to the weight [unit 4 q + i][col] (col < K), to that
 // unit's bias (col == K) or to nothing; the upstream rows of masked rows are 0, so the column of
-// ones is 1 in every row.  grad: null or the step's gradient, gw / gb the layer's places in it.
+// ones is 1 in every row.
+__device__ __forceinline__ floatx4 wgrad_prod(int K, int col, const float* gl, int gld, int goff, const float* bl,
+                                              int bld, int boff, int r, int q) {
+    const int lc = col < K ? col - boff : 0;   // a tile column that exists (col >= K: not used)
+    floatx4 acc = zero4();
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int row = 4 * s + q;
+        const float b = bl[row * bld + lc];
+        acc = mfma4(gl[row * gld + goff + r], col < K ? b : (col == K ? 1.f : 0.f), acc);
+    }
+    return acc;
+}
+
+// One job and Adam (hp) on its elements: the 16 units 16 ublk .. + 15 of the layer whose weight
+// tensor is t (U units, K inputs) against the 16 columns col0 .. + 15 of [input, 1] (wgrad_prod).
+// grad: null or the step's gradient, gw / gb the layer's places in it.
 __device__ __forceinline__ void wgrad_job(const StepArgs& a, const AdamK& hp, float* grad, int t, int U, int K,
                                           int ublk, int col0, const float* gl, int gld, int goff, const float* bl,
                                           int bld, int boff, int64_t gw, int64_t gb, int r, int q) {
@@ -119,14 +242,7 @@ __device__ __forceinline__ void wgrad_job(const StepArgs& a, const AdamK& hp, fl
         pm[i][1] = (bias ? mb : mw)[e];
         pm[i][2] = (bias ? vb : vw)[e];
     }
-    const int lc = col < K ? col - boff : 0;   // a tile column that exists (col >= K: not used)
-    floatx4 acc = zero4();
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        const int row = 4 * s + q;
-        const float b = bl[row * bld + lc];
-        acc = mfma4(gl[row * gld + goff + r], col < K ? b : (col == K ? 1.f : 0.f), acc);
-    }
+    const floatx4 acc = wgrad_prod(K, col, gl, gld, goff, bl, bld, boff, r, q);
     if (col <= K) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -137,21 +253,14 @@ __device__ __forceinline__ void wgrad_job(const StepArgs& a, const AdamK& hp, fl
     }
 }
 
-// wgrad_job's product without the step (policy_fit_rows.hip: Adam follows a kernel boundary, on
-// the gradients of all row tiles folded): the job's accumulator, formed exactly as there, goes to
-// its flat place gw / gb of one row tile's [d] slice of the scratch, which starts at float off.
+// The job without the step (policy_fit_rows.hip: Adam follows a kernel boundary, on the gradients
+// of all row tiles folded): the same accumulator goes to its flat place gw / gb of one row tile's
+// [d] slice of the scratch, which starts at float off.
 __device__ __forceinline__ void wgrad_store_job(const StepArgs& a, int64_t off, int U, int K, int ublk, int col0,
                                                 const float* gl, int gld, int goff, const float* bl, int bld,
                                                 int boff, int64_t gw, int64_t gb, int r, int q) {
     const int col = col0 + r;
-    const int lc = col < K ? col - boff : 0;   // a tile column that exists (col >= K: not used)
-    floatx4 acc = zero4();
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        const int row = 4 * s + q;
-        const float b = bl[row * bld + lc];
-        acc = mfma4(gl[row * gld + goff + r], col < K ? b : (col == K ? 1.f : 0.f), acc);
-    }
+    const floatx4 acc = wgrad_prod(K, col, gl, gld, goff, bl, bld, boff, r, q);
     if (col <= K) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -160,6 +269,51 @@ __device__ __forceinline__ void wgrad_store_job(const StepArgs& a, int64_t off, 
             const int64_t e = off + (col < K ? gw + (int64_t)unit * K + col : gb + unit);
             MJRL_SLAB_CHECK(e, a.scap);
             a.scratch[e] = acc[i];
+        }
+    }
+}
+
+// the LDS tiles of a one-workgroup chain: xhat (one chunk of columns, pitch PS_XLD), then pitch PS_LD
+struct ChainTiles {
+    float *Xs, *a0s, *a1s, *g0s, *g1s, *zs;   // zs: z, then gmu
+};
+
+// Phase 9's walk of wave w (of PS_THREADS / 64) over the 16 x 16 jobs of a step: dW2 = gmu^T [a1, 1],
+// dW1 = g1^T [a0, 1], dW0 = g0^T [xhat, 1] chunk by chunk, the last forward chunk first (it is
+// still in LDS); the bias sums ride along as a column of ones.  load(c): stage chunk c of xhat;
+// job(t, U, K, jub, col0, gl, bl, bld, boff, gw, gb): the units 16 jub .. + 15 of the layer whose
+// weight tensor is t (upstream tile gl, pitch PS_LD) against 16 columns of [input, 1];
+// stamp(i): the phase profile's stamp i (profiling builds of k_pfit).
+template <class Load, class Job, class Stamp>
+__device__ __forceinline__ void wgrad_walk(int n, int m, int h0, int h1, int w, const ChainTiles& t, const GradAt& o,
+                                           const Load& load, const Job& job, const Stamp& stamp) {
+    constexpr int XCW = PS_XCW;
+    const int UB0 = (h0 + 15) / 16, UB1 = (h1 + 15) / 16, UB2 = (m + 15) / 16;   // unit blocks
+    const int CB2 = h1 / 16 + 1, CB1 = h0 / 16 + 1;   // column blocks of [a1, 1], [a0, 1]
+    const int nj2 = UB2 * CB2, nj1 = UB1 * CB1;
+    const int nchunk_b = n / XCW + 1;   // backward chunks: the column of ones (col n) counts
+    int resident = (n + XCW - 1) / XCW - 1;   // the last forward chunk
+    for (int c = nchunk_b - 1; c >= 0; --c) {
+        if (c != resident && n > c * XCW) {   // (a chunk holding only the column of ones needs no tile)
+            stamp(10);
+            __syncthreads();   // the previous chunk's jobs have read Xs
+            stamp(13);
+            load(c);
+            __syncthreads();
+            resident = c;
+            stamp(9);
+        }
+        const int cb0 = n / 16 + 1 - c * (XCW / 16);          // layer 0's column blocks from this chunk on
+        const int nb0 = cb0 < XCW / 16 ? cb0 : XCW / 16;
+        const int nj0 = UB0 * nb0;
+        const int nj = nj0 + (c == nchunk_b - 1 ? nj2 + nj1 : 0);   // the first chunk visited carries layers 2 and 1
+        for (int j = w; j < nj; j += PS_THREADS / 64) {
+            if (j < nj0)
+                job(0, h0, n, j / nb0, c * XCW + 16 * (j % nb0), t.g0s, t.Xs, PS_XLD, c * XCW, 0, o.b0);
+            else if (j < nj0 + nj2)
+                job(4, m, h1, (j - nj0) / CB2, 16 * ((j - nj0) % CB2), t.zs, t.a1s, PS_LD, 0, o.W2, o.b2);
+            else
+                job(2, h1, h0, (j - nj0 - nj2) / CB1, 16 * ((j - nj0 - nj2) % CB1), t.g1s, t.a0s, PS_LD, 0, o.W1, o.b1);
         }
     }
 }
@@ -275,20 +429,25 @@ __device__ __forceinline__ void head_rows(const StepArgs& a, bool aliased, int t
     }
 }
 
+// d log_std of column lane over the 64 rows (0 from column m on), by one wave
+template <int ZLD>
+__device__ __forceinline__ float head_dls(int m, int lane, const float* zs, const float* s_gll) {
+    if (lane >= m) return 0.f;
+    double s = 0.0;
+    for (int row = 0; row < PS_ROWS; ++row) {
+        const double z = (double)zs[row * ZLD + lane];
+        s += (double)s_gll[row] * (z * z - 1.0);
+    }
+    return (float)s;
+}
+
 // d log_std (wave 0: the value returned) and the step's loss (wave 1) into scratch[slot] and *loss (or null)
 template <bool MSE, int ZLD>
 __device__ __forceinline__ float head_sums(const StepArgs& a, int w, int lane, const float* zs, const float* s_gll,
                                            const double* s_lossd, int slot, float* loss) {
     float dls = 0.f;
     if (!MSE && w == 0) {
-        if (lane < a.na) {
-            double s = 0.0;
-            for (int row = 0; row < PS_ROWS; ++row) {
-                const double z = (double)zs[row * ZLD + lane];
-                s += (double)s_gll[row] * (z * z - 1.0);
-            }
-            dls = (float)s;
-        }
+        dls = head_dls<ZLD>(a.na, lane, zs, s_gll);
     } else if (w == 1) {
         const double tot = wave_sum(s_lossd[lane]) / (double)a.bs;
         if (lane == 0) {
@@ -397,7 +556,7 @@ inline int step_args(StepArgs& a, const mjrl_policy_fit_data* data, const int64_
     a.h0 = h0;
     a.h1 = h1;
     a.bs = bs;
-    a.d = (int64_t)h0 * n + h0 + (int64_t)h1 * h0 + h1 + (int64_t)na * h1 + na + (MSE ? 0 : na);
+    a.d = grad_at(n, na, h0, h1, MSE).d;
     const auto al16 = [](const void* q) { return (uintptr_t)q % 16 == 0; };
     a.vx = n % 4 == 0 && al16(data->obs) && al16(data->in_shift) && al16(data->in_scale);
     a.vw0 = n % 4 == 0 && al16(a.p[0]);
