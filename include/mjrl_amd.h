@@ -563,6 +563,23 @@ int mjrl_policy_act(const mjrl_shape* s, const void* obs, int32_t obs_f64, int64
                     const float* sigma, uint64_t seed, int64_t step, int64_t env0, void* act, float* mean,
                     float* eps, void* obs_copy, void* stream);
 
+/* ---- minibatch row indices drawn on the device (csrc/minibatch.hip) ----
+ * What np.random.choice(T, mb) gives PPO per minibatch (mjrl/algos/ppo_clip.py:90-91),
+ * uniform on [0, T) with replacement, as a counter-based stream: idx[i] = draw
+ * g = first + i of the stream of `seed`, i < count.  Draw g is a function of (seed, g,
+ * T) alone, so splitting the draws over launches, epochs and calls changes no bit:
+ *   block b = g >> 1; (x0 .. x3) = Philox4x32-10 of the counter (b lo, b hi, 0, 0) under
+ *   the key (seed lo, seed hi ^ 0x4D425849) (the constant keeps the stream apart from
+ *   mjrl_policy_act's noise under the same seed);
+ *   u = x0 | x1 << 32 for even g, x2 | x3 << 32 for odd g;
+ *   index = the high 64 bits of u * T (bias at most T / 2^64)
+ * (algos/_device_sgd.py: minibatch_indices_reference restates it in NumPy).  idx is a
+ * device pointer to count int64; nothing outside idx[0 .. count) is written.
+ * Stream-ordered, no allocation, no synchronisation.  MJRL_EINVAL before any launch
+ * for T < 1, first < 0, count < 0, first + count above 2^63 - 1, or a null idx with
+ * count > 0; count == 0 is MJRL_OK without a launch. */
+int mjrl_minibatch_indices(uint64_t seed, int64_t first, int64_t count, int64_t T, int64_t* idx, void* stream);
+
 /* ---- MLPBaseline value features formed while sampling (streamed staging) ----
  * The first n columns of mjrl/baselines/mlp_baseline.py:37-56's features,
  * float32(clip(x, -10, 10) / 10) of the sampler's f64 observation x (no f32 image of

@@ -159,6 +159,7 @@ SIGNATURES = {
     "mjrl_policy_mean": [SP, P, I64, P, P, P, P, P, P, P],
     "mjrl_policy_mean_slots": [SP, P, P, I64, I64, P, P, P, P, P, P, P],
     "mjrl_policy_act": [SP, P, I32, I64, P, P, P, P, P, P, C.c_uint64, I64, I64, P, P, P, P, P],
+    "mjrl_minibatch_indices": [C.c_uint64, I64, I64, I64, P, P],
     "mjrl_value_features_slots": [P, P, P, I64, I64, I32, I64, P, P],
     "mjrl_value_features_finish": [P, P, I64, I32, I64, I64, P, P, P],
     "mjrl_value_features_finish_runs": [P, P, I64, I32, I64, I64, I64, P, P, P],

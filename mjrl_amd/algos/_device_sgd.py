@@ -14,7 +14,10 @@ mean (functional form of MuNet / LinearModel, gaussian_mlp.py:143-182), the
 loss, backward, the optimizer step — is captured once as a hipGraph and replayed
 per minibatch (capturable Adam); the minibatch indices come from numpy's global
 RNG in the reference's order, drawn for a whole epoch up front and uploaded in one
-copy.  Optimizers without a capturable mode run the same step eagerly.
+copy (choice_batches), or, with PPO.minibatch_draw = "device", drawn on the device by
+one launch per epoch from a counter-based stream of the agent's own (csrc/minibatch.hip,
+device_choice_batches; minibatch_indices_reference states the draw in NumPy).
+Optimizers without a capturable mode run the same step eagerly.
 
 fit_backend = "hip" on BC / PPO (opt-in) replaces the graph replays of an epoch by
 one mjrl_policy_fit_epoch call (csrc/policy_fit.hip) on the same device
@@ -299,3 +302,58 @@ def choice_batches(num_samples, mb_size, device):
         return torch.zeros((0, mb_size), dtype=torch.int64, device=device)
     idx = np.stack([np.random.choice(num_samples, size=mb_size) for _ in range(nmb)]).astype(np.int64)
     return torch.from_numpy(idx).to(device)
+
+
+# PPO.minibatch_draw: "numpy" is choice_batches above, "device" the counter-based
+# stream of csrc/minibatch.hip (device_choice_batches)
+MINIBATCH_DRAWS = ("numpy", "device")
+DRAW_KEY_TAG = 0x4D425849   # "MBXI": keeps the draws' stream apart from the actor's noise under one seed
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _mulhi64(u, t):
+    """The high 64 bits of u * t, u a uint64 array and t an int in [0, 2^64), on
+    32-bit limbs (every partial product and sum fits a uint64)."""
+    ul, uh = u & _M32, u >> _S32
+    tl, th = np.uint64(t & 0xFFFFFFFF), np.uint64(t >> 32)
+    lh, hl = ul * th, uh * tl
+    carry = ((ul * tl >> _S32) + (lh & _M32) + (hl & _M32)) >> _S32
+    return uh * th + (lh >> _S32) + (hl >> _S32) + carry
+
+
+def minibatch_indices_reference(seed, first, count, T):
+    """The definition of mjrl_minibatch_indices (csrc/minibatch.hip) in NumPy: draws
+    first .. first + count - 1 of the stream of `seed`, int64 [count], each uniform on
+    [0, T) with replacement as np.random.choice(T, mb) is.  Draw g is a function of
+    (seed, g, T) alone: block b = g >> 1 of Philox4x32-10 on the counter (b lo, b hi, 0,
+    0) under the key (seed lo, seed hi ^ DRAW_KEY_TAG), u = x0 | x1 << 32 for even g and
+    x2 | x3 << 32 for odd g, the index the high 64 bits of u T (bias at most T / 2^64).
+    Never loads the GPU library."""
+    from ..samplers.device_actor import philox4x32
+    seed, first, count, T = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), int(T)
+    if T < 1 or first < 0 or count < 0 or first + count > 2 ** 63 - 1:
+        raise ValueError("minibatch_indices_reference needs T >= 1, first >= 0, count >= 0 and draws below 2^63, "
+                         "got %d, %d, %d" % (T, first, count))
+    g = first + np.arange(count, dtype=np.int64)
+    b = (g >> 1).astype(np.uint64)
+    x = philox4x32((b & _M32, b >> _S32, 0 * b, 0 * b), (seed & 0xFFFFFFFF, (seed >> 32) ^ DRAW_KEY_TAG))
+    odd = (g & 1).astype(bool)
+    u = np.where(odd, x[2], x[0]).astype(np.uint64) | np.where(odd, x[3], x[1]).astype(np.uint64) << _S32
+    return _mulhi64(u, T).astype(np.int64)
+
+
+def device_choice_batches(seed, first, num_samples, mb_size, device):
+    """choice_batches' [nmb][mb] device tensor for one epoch, drawn on the device
+    (mjrl_minibatch_indices on the current stream: no host RNG, no upload): draws first
+    .. first + nmb mb - 1 of the stream of `seed` (minibatch_indices_reference,
+    reshaped).  Returns (the tensor, the next first)."""
+    from .. import _lib
+    device = torch.device(device)
+    nmb = int(num_samples / mb_size)
+    out = torch.empty((nmb, mb_size), dtype=torch.int64, device=device)
+    if nmb:
+        with torch.cuda.device(device):
+            _lib.calls().mjrl_minibatch_indices(int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), nmb * mb_size,
+                                                int(num_samples), out, _lib.stream_ptr())
+    return out, int(first) + nmb * mb_size

@@ -450,15 +450,13 @@ class BatchREINFORCE:
         the update: the update itself reads GAE advantages, which bootstrap
         already); needs gae_lambda in [0, 1], as plain advantages are returns -
         baseline with the unbootstrapped returns.
-        BatchREINFORCE, NPG and TRPO with a LinearBaseline, a ZeroBaseline or no
-        baseline, on one GPU in this process."""
+        BatchREINFORCE, NPG, TRPO and PPO (its own update between the ingest and the
+        fit: ppo_clip.py) with a LinearBaseline, a ZeroBaseline or no baseline, on one
+        GPU in this process."""
         for k in type(self).__mro__:
             if k.__name__ == "DAPG":
                 raise ValueError("%s.train_from_rollout: DAPG's demonstration rows are host paths; use train_step / "
                                  "train_from_paths" % type(self).__name__)
-            if k.__name__ == "PPO":
-                raise ValueError("%s.train_from_rollout: PPO's update works on path dicts; use train_from_paths "
-                                 "(rollout_ingest.rollout_to_paths makes them)" % type(self).__name__)
         from ..comm import launched_world
         from ..pool import resolve_devices
         lw = launched_world()
@@ -474,7 +472,7 @@ class BatchREINFORCE:
             raise ValueError("%s.train_from_rollout: bootstrap_returns needs GAE (gae_lambda in [0, 1], got %r): "
                              "plain advantages are returns - baseline and would read the unbootstrapped returns"
                              % (type(self).__name__, gae_lambda))
-        DeviceBatch.check_rollout(observations, actions, rewards, done, terminated, steps, self.baseline, carry)
+        self._check_rollout(observations, actions, rewards, done, terminated, steps, self.baseline, carry)
         if self.comm().world_size > 1:   # a process group initialised by the caller
             raise ValueError("%s.train_from_rollout: world size %d: sharded runs take host paths (train_step)"
                              % (type(self).__name__, self.comm().world_size))
@@ -500,6 +498,11 @@ class BatchREINFORCE:
                 self.logger.log_kv("VF_error_before", err[0])
                 self.logger.log_kv("VF_error_after", err[1])
         return out
+
+    def _check_rollout(self, *args):
+        """The rollout's argument checks, made without loading the GPU library (PPO
+        puts its class name on their errors)."""
+        return DeviceBatch.check_rollout(*args)
 
     def _episode_statistics(self, batch, carry):
         """Whole-episode returns of a carried rollout, on the device without a host

@@ -21,8 +21,8 @@ FLAGS = [
     "-ffp-contract=off",          # keep the reference's multiply-then-add order
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
 ]
-SOURCES = ["batch.hip", "policy.hip", "cg.hip", "baseline.hip", "rollout.hip", "act.hip", "ingest.hip", "value_fit.hip",
-           "policy_fit.hip", "policy_fit_wide.hip", "policy_fit_rows.hip"]
+SOURCES = ["batch.hip", "policy.hip", "cg.hip", "baseline.hip", "rollout.hip", "act.hip", "minibatch.hip", "ingest.hip",
+           "value_fit.hip", "policy_fit.hip", "policy_fit_wide.hip", "policy_fit_rows.hip"]
 # host-only C++ (the staging conversion of csrc/stage.cpp), built with g++
 HOST_SOURCES = ["stage.cpp"]
 # no -m flag: the AVX-512 path is selected at run time (csrc/stage.cpp)

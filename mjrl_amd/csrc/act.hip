@@ -22,6 +22,7 @@
 //
 // No grid barrier, no atomics, no spin loops: plain vector stores only.
 #include "common.h"
+#include "philox.h"
 
 using namespace mjrl;
 
@@ -31,21 +32,6 @@ constexpr int ACT_BT = 16;    // rows per workgroup: 256 tiles at E = 4096, one 
 constexpr int ACT_KC = 128;   // observation columns staged per chunk (a multiple of 16)
 constexpr int ACT_LDX = ACT_KC + 4;
 constexpr int ACT_NCB = 4;    // first-layer column blocks per wave: widths up to 16 * 4 * ACT_NCB = 256
-
-// Philox4x32-10 (Salmon et al., SC'11; Random123's philox4x32_R(10, ...)).
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
-        c[0] = h1 ^ c[1] ^ k0;
-        c[1] = l1;
-        c[2] = h0 ^ c[3] ^ k1;
-        c[3] = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 
 // The standard normal of column j (element j & 3 of its block of four) from the
 // block's four words: Box-Muller on the pair (x0, x1) or (x2, x3), u1 = ((x >> 8) + 1)

@@ -465,6 +465,13 @@ _Update = collections.namedtuple("_Update", (
     "residual_tol", "learn_rate", "skip_gae", "demo_coef", "T_global", "sub"))
 
 
+def _path_return_stats(stats):
+    """[mean, std, min, max] of the path returns (npg_cg.py:97-102) from the host copy
+    of the moment records the advantage stage leaves at S_PM1 / S_PM2."""
+    n_p = stats[S_PM1 + 2]
+    return [stats[S_PM1] / n_p, math.sqrt(stats[S_PM2 + 1] / n_p), -stats[S_PM1 + 5], stats[S_PM1 + 4]]
+
+
 def _normalize(K, x, T, part, m1, m2, out, st, allreduce=None):
     """out = (x - mean) / (std + 1e-8) over the T f64 values of x
     (process_samples.py:14-19, 30-35): two-pass fp64 moments into the records m1 /
@@ -1545,8 +1552,7 @@ class UpdateEngine:
             np.random.set_state(sub["rng"])
             for _ in range(int(cg[1])):
                 np.random.choice(sub["N"], size=sub["Ts"])
-        n_p = stats[S_PM1 + 2]
-        base_stats = [stats[S_PM1] / n_p, math.sqrt(stats[S_PM2 + 1] / n_p), -stats[S_PM1 + 5], stats[S_PM1 + 4]]
+        base_stats = _path_return_stats(stats)
         result = dict(
             alpha=float(out[0]),
             gx=float(out[1]),
@@ -1778,6 +1784,30 @@ class UpdateEngine:
         else:
             self.ws["adv32"][:T].zero_()
         return T
+
+    @_on_device
+    def load_batch(self, batch, theta, gamma=0.995, gae_lambda=0.98):
+        """The current rows from a batch that is already in HBM (PPO's device-rollout
+        update), with no host copy: the update's own advantage stage (a1-a5: GAE,
+        returns, batch assembly, moments, whitening; the whitened f32 advantages stay in
+        ws['adv32'], the path-return moments in the statistics, see path_return_stats)
+        and its forward pass at theta, which fills the caches as forward_pass does.
+        eval_pass / forward_pass then run over these rows.  Returns T."""
+        main = torch.cuda.current_stream(self.device)
+        st = C.c_void_p(main.cuda_stream)
+        T = batch.T
+        self._ensure(T + batch.T_demo, batch.P)
+        u = _Update(batch, "vpg", gamma, gae_lambda, None, None, None, 0, 0.0, 0.0, 0.0, False, None, float(T), None)
+        fused, adv, T_vpg = self._stage_advantages(u, main, st)
+        self.last_T, self.last_T_global = T, float(T)
+        self._stage_vpg(u, self._pad(theta, "theta"), fused, self._rows(T_vpg, adv), self._scratch(T_vpg),
+                        [_NoEvent()] * 2, st)
+        return T
+
+    def path_return_stats(self):
+        """[mean, std, min, max] of the path returns of the last advantage stage (update
+        or load_batch), as update's base_stats: one readback of the statistics."""
+        return [float(v) for v in _path_return_stats(self.stats.cpu().numpy())]
 
     @_on_device
     def forward_pass(self, theta, T):
